@@ -37,6 +37,7 @@ N_PEOPLE, T_LOCAL, IMG, BATCH = 4, 200, (240, 135), 10
 PEAK_HBM_GBS = 8000.0
 PEAK_F32_MFMA_TFLOPS = 157.3
 PEAK_VALU_GIPS = 614.4     # 256 CUs x 4 SIMDs x 2.4 GHz, one wave64 vector instruction per 4 cycles
+PROD_CYCLES = 2            # untimed cycles on the production gradient scatter right before the timed ones (see main)
 
 
 def build_optimizer(struct, regs, tmp, num_frames, device, K):
@@ -177,7 +178,12 @@ def main():
     ap.add_argument('--presteps', type=int, default=300, help='untimed steady-state cycles before the warm-up')
     ap.add_argument('--dump-leaves', type=str, default=None, help='(parity tests) save the whole-sequence leaves after the timed '
                     'region to this .npz (a collective in multi-rank runs; rank 0 writes)')
+    ap.add_argument('--dump-outputs', type=str, default=None, metavar='DIR', help='after the timed steps, write what the last '
+                    'one handed its caller -- the optimised variables and that step\'s loss log -- as DIR/<name>.npy (see '
+                    'dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     global N_PEOPLE, T_LOCAL, IMG
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without a launcher: become N ranks (one process per GPU) under torch.distributed.run,
@@ -339,13 +345,23 @@ def main():
         e.grads.zero_()
     # bring the device to its steady state before the W warm-up steps: graph capture, lazy allocations, and enough
     # back-to-back work for the clocks to ramp (a fresh box that idled through the CPU-side set-up was once measured
-    # at 0.57x for the first tens of milliseconds)
-    for c_pre in range(args.presteps):  # a fixed count: every rank must issue the same collectives
-        one_cycle(1 + c_pre % 20, use_graphs)
-        if c_pre % 10 == 9:
-            torch.cuda.synchronize()
-    for c in range(args.warmup):
+    # at 0.57x for the first tens of milliseconds).  The untimed cycles but the last PROD_CYCLES sum the rasteriser's gradient
+    # scatter in fixed point (bit-reproducible): RMSprop's first, sign-like steps turn the rounding of fp32 atomics into a
+    # different trajectory in every run, so without it the timed cycles would start from a different state every run --
+    # other work, and other outputs for --dump-outputs.  The last PROD_CYCLES untimed cycles switch back to the production
+    # scatter: the first captures its graph, the second replays it, so the timed cycles run exactly as they would without
+    # this, from nearly the same state every run (those two cycles carry the rounding of the fp32 atomics, as the timed
+    # ones do, and each more of them widens the spread of two runs' outputs).
+    from mhhip.raster import set_deterministic
+    untimed = [(1 + c_pre % 20, c_pre % 10 == 9) for c_pre in range(args.presteps)] + [(c, False) for c in range(args.warmup)]
+    prod_det = set_deterministic(True)
+    for i, (c, sync) in enumerate(untimed):  # a fixed count: every rank must issue the same collectives
+        if i == max(0, len(untimed) - PROD_CYCLES):
+            set_deterministic(prod_det)
         one_cycle(c, use_graphs)
+        if sync:
+            torch.cuda.synchronize()
+    set_deterministic(prod_det)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -361,6 +377,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
         opt.check_replicas()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, opt, sh, args.warmup + args.steps - 1, rank)
     if args.dump_leaves:
         opt._global_cache = None
         g_all = opt._global_leaves()              # collective
@@ -627,6 +645,38 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(path, opt, sh, cycle, rank):
+    """--dump-outputs: what the timed path handed its caller after its last step (cycle ``cycle``), for comparing two builds
+    output for output on the same seeded inputs -- the optimised variables ``get_optimized_variables()`` returns (float32)
+    and the step's loss log entries (``log_<key>.npy``, float32 scalars).  Above DUMP_BYTES in all, the per-frame arrays keep
+    the same seeded sample of frames, whose indices are in ``frames_sampled.npy``.  A collective in multi-rank runs (the
+    whole-sequence leaves are gathered, the log rows reduced); rank 0 writes."""
+    opt._global_cache = None
+    opt._global_leaves()                  # (multi-rank: gathers the copy get_optimized_variables() reads)
+    row = cycle % opt.engine.log.shape[0]
+    log = sh.read_log(row + 1)[row]
+    if rank != 0:
+        return
+    ov = opt.get_optimized_variables()
+    out = {k: np.asarray(ov[k], np.float32) for k in ('poses_T', 'poses_smpl', 'betas_smpl', 'scale_factor', 'min_z', 'max_z')}
+    T = opt.num_frames
+    per_frame = [k for k, a in out.items() if T > 1 and a.shape[:1] == (T,)]
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES:
+        frame_bytes = sum(out[k].nbytes for k in per_frame) // T
+        keep = (DUMP_BYTES - (total - frame_bytes * T)) // (frame_bytes + 8)
+        idx = np.sort(np.random.RandomState(0).choice(T, keep, replace=False))
+        out.update({k: out[k][idx] for k in per_frame})
+        out['frames_sampled'] = idx.astype(np.float64)
+    out.update({'log_' + k: np.asarray(v, np.float32) for k, v in log.items()})
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + '.npy'), a)
 
 
 def fit_block(struct, regs, tmp, device, K, seq):

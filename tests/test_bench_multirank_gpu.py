@@ -3,7 +3,11 @@ exactly as the driver launches the scaling bench, with ``--backend gloo --one-de
 host, all ranks on cuda:0 -- RCCL refuses two ranks per device and this box has one GPU).  Everything except the RCCL
 transport itself runs: the drop-in's own sharding of ONE contiguous sequence, uneven blocks, middle ranks with two
 neighbours, the multi-hop one-euro hand-off, halos between the captured graphs, the all-reduce per cycle, replica check,
-weak (default / --config c4) and strong (--strong) accounting of the JSON line.  Toy sizes; the numbers are not results."""
+weak (default / --config c4) and strong (--strong) accounting of the JSON line.  Toy sizes; the numbers are not results.
+
+No test here runs more than MAX_RANKS ranks: with the pytest process and the launcher, which hold the GPU as well, that is
+five processes with the GPU open at once.  The GPU machines this suite is checked on stop a job that holds more than six
+(eight ranks made ten); four ranks would hold exactly six."""
 import json
 import os
 import subprocess
@@ -13,6 +17,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MAX_RANKS = 3
 
 
 def _run(nproc, extra, port):
@@ -53,9 +58,9 @@ def test_weak_scaling_form_on_three_ranks():
 
 
 @pytest.mark.timeout(1800)
-def test_c4_form_on_eight_ranks():
-    out = _run(8, ['--config', 'c4', '--frames', '10'], 29823)
-    assert out['n_gpus'] == 8 and out['config']['frames'] == 80 and out['scaling'] == 'weak'
+def test_c4_form_on_three_ranks():
+    out = _run(MAX_RANKS, ['--config', 'c4', '--frames', '10'], 29823)
+    assert out['n_gpus'] == MAX_RANKS and out['config']['frames'] == 10 * MAX_RANKS and out['scaling'] == 'weak'
     assert out['loss_first_cycle']['reg_filter_verts'] > 0 and out['loss_first_cycle']['reg_contact'] > 0
 
 
@@ -70,17 +75,18 @@ def test_strong_scaling_form_uneven_shards():
 
 
 @pytest.mark.timeout(3000)
-def test_c4_at_full_size_eight_ranks_equal_one_process(tmp_path):
-    """BASELINE C4 exactly -- 4 humans x 2000 frames at 240x135, 250 frames per rank -- as eight ranks on this one device
-    (gloo, collectives through the host: everything but the RCCL transport) against the SAME 4 x 2000 sequence in one
+def test_c4_at_full_size_three_ranks_equal_one_process(tmp_path):
+    """BASELINE C4's ranks at full size -- 4 humans x 250 frames at 240x135 per rank -- as three ranks on this one device
+    (gloo, collectives through the host: everything but the RCCL transport) against the SAME 4 x 750 sequence in one
     process on the same GPU: the nine-term stack, kept face lists, the projection epilogue, one graph and one all-reduce
-    per cycle on the eight ranks.  VERDICT r03: the multi-rank maths had only ever run at toy sizes.
+    per cycle on the three ranks.  VERDICT r03: the multi-rank maths had only ever run at toy sizes.  (C4 itself is eight
+    such ranks; eight ranks on one device hold the GPU in more processes than the six the module docstring names.)
 
     (1) THE MATHS: the gradient of every leaf of one unstepped cycle at identical variables (deterministic scatter).
     (2) THE TRAJECTORIES, 18 cycles and a one-euro filter update later, against what two runs of the one-process job part by.
 
-    Until round 4 this test had to repeat the eight-rank run: a few frames -- different ones every time -- came out with
-    different selection keys.  It was not the eight processes: the frame-sharded cycle skins its neighbours' boundary frames
+    Until round 4 this test had to repeat the multi-rank run: a few frames -- different ones every time -- came out with
+    different selection keys.  It was not the processes: the frame-sharded cycle skins its neighbours' boundary frames
     in the side branch, beside the selection kernel, and hipcc had packed part of that kernel's fp32 arithmetic
     (``v_pk_*_f32``), which returns wrong values while another wave's matrix instructions are in flight on the same SIMD
     (mhhip/build.py, tests/test_corunner_gpu.py).  Without packed instructions the FIRST run must be
@@ -90,19 +96,19 @@ def test_c4_at_full_size_eight_ranks_equal_one_process(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', OMP_NUM_THREADS='2')
 
     def run_one(path):
-        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--frames', '2000', '--dump-leaves', path] + common,
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--frames', str(250 * MAX_RANKS), '--dump-leaves', path] + common,
                            cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1400)
         assert p.returncode == 0, p.stderr[-3000:]
         return np.load(path)
 
-    def run_eight(path, port):
-        cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '8', '--master-addr', '127.0.0.1',
-               '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--backend', 'gloo', '--one-device', '--config', 'c4',
-               '--dump-leaves', path] + common
+    def run_ranks(path, port):
+        cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(MAX_RANKS), '--master-addr', '127.0.0.1',
+               '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', str(MAX_RANKS), '--backend', 'gloo', '--one-device',
+               '--config', 'c4', '--dump-leaves', path] + common
         p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1400)
         assert p.returncode == 0, p.stderr[-3000:]
         out = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
-        assert out['n_gpus'] == 8 and out['config']['frames'] == 2000 and out['config']['frames_per_gpu'] == 250
+        assert out['n_gpus'] == MAX_RANKS and out['config']['frames'] == 250 * MAX_RANKS and out['config']['frames_per_gpu'] == 250
         return np.load(path)
 
     a = run_one(str(tmp_path / 'one.npz'))
@@ -110,17 +116,17 @@ def test_c4_at_full_size_eight_ranks_equal_one_process(tmp_path):
     GRADS = ('grad0_poses_T', 'grad0_poses_smpl', 'grad0_zmin_lin', 'grad0_zmax_lin', 'grad0_tail')
     for k in GRADS:
         assert np.array_equal(a[k], c[k]), k                   # one process: bit-identical from run to run
-    b = run_eight(str(tmp_path / 'eight.npz'), 29851)
-    # the LBS backward cuts the vertices into 500 / (groups of 32 bodies) chunks and adds the chunk sums in order: 2 chunks for
-    # the one process' 250 groups, 16 for a rank's 32, so sums of 6890 cancelling terms round differently; the shared tail is
+    b = run_ranks(str(tmp_path / 'ranks.npz'), 29851)
+    # the LBS backward cuts the vertices into 500 / (groups of 32 bodies) chunks and adds the chunk sums in order: 6 chunks for
+    # the one process' 94 groups, 16 for a rank's 32, so sums of 6890 cancelling terms round differently; the shared tail is
     # additionally summed per rank and then across ranks
     worst = {k: float(np.abs(a[k] - b[k]).max() / np.abs(a[k]).max()) for k in GRADS}
-    print('first-cycle gradients, max |eight ranks - one process| / largest entry: %s' % ', '.join('%s %.1e' % (k[6:], v) for k, v in worst.items()))
-    assert max(worst.values()) <= 2e-5, 'first-cycle gradients of the eight-rank run differ from the one-process run: %s' % worst
+    print('first-cycle gradients, max |%d ranks - one process| / largest entry: %s' % (MAX_RANKS, ', '.join('%s %.1e' % (k[6:], v) for k, v in worst.items())))
+    assert max(worst.values()) <= 2e-5, 'first-cycle gradients of the multi-rank run differ from the one-process run: %s' % worst
     for k in ('poses_T', 'poses_smpl', 'betas', 'zmin_lin', 'zmax_lin', 'xscale'):
         assert a[k].shape == b[k].shape, k
         d, d1 = np.abs(a[k] - b[k]), np.abs(a[k] - c[k])
-        print('%-10s |eight ranks - one process|: median %.2e  99%% %.2e  max %.2e   (one process twice: median %.2e  99%% %.2e  max %.2e)'
+        print('%-10s |ranks - one process|: median %.2e  99%% %.2e  max %.2e   (one process twice: median %.2e  99%% %.2e  max %.2e)'
               % (k, np.median(d), np.percentile(d, 99), d.max(), np.median(d1), np.percentile(d1, 99), d1.max()))
         # RMSprop's first steps are sign-like (g / sqrt(0.5 g^2)): an entry whose gradient is rounding noise moves by +-lr whichever
         # way the noise points, so single entries part by centimetres in ANY two runs (the float atomics of the production scatter

@@ -10,7 +10,8 @@ pytestmark = pytest.mark.gpu
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_pytorch3d.npz')
 
 
-@pytest.mark.skipif(not os.path.exists(FIX), reason='tests/golden/reference_pytorch3d.npz not generated yet')
+@pytest.mark.skipif(not os.path.exists(FIX), reason='tests/golden/reference_pytorch3d.npz not generated yet (python '
+                    'tests/golden/make_golden_pytorch3d.py where PyTorch3D is installed)')
 @pytest.mark.parametrize('name', ['cross', 'por', 'sq'])
 def test_hip_depth_and_silhouette_match_pytorch3d(smpl_struct, smpl_regs, name):
     from mhhip import engine

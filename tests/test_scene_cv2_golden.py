@@ -61,7 +61,7 @@ def test_restated_primitives_match_opencv(cvf, i):
 def test_whole_postprocess_matches_the_reference_with_opencv(cvf, i):
     key = 'm%d_ref_post' % i
     if key not in cvf:
-        pytest.skip('the fixture was generated without /root/reference: primitives only')
+        pytest.skip('the fixture was generated without the reference tree: primitives only')
     got = so.postprocess_depthmap(cvf['m%d_depth' % i], cvf['m%d_mask' % i], fillin_ksize=7, use_bilateral_filter=True)
     want = cvf[key]
     # the edge threshold (3 x mean of the gradient measure) may flip a borderline pixel and with it its fill: all but a
