@@ -96,10 +96,6 @@ int mh_stream_destroy(void* stream);
 int mh_streams_share_queue(void* stream_a, void* stream_b, float spin_us, int* shared);
 /* one spin kernel (one thread) of ~spin_us on the stream, asynchronous: keeps the stream's hardware queue busy */
 int mh_stream_spin(void* stream, float spin_us);
-/* shared = 1 when x drains through the hardware queue of ANY of busy[0 .. n), n <= 8 (all spin at once: one probe) */
-int mh_stream_shares_any(void* const* busy, int n, void* x, float spin_us, int* shared);
-/* the same for m <= 32 candidates in one probe: shared[j] = 1 when cand[j] shares a hardware queue with any busy stream */
-int mh_streams_classify(void* const* busy, int n, void* const* cand, int m, float spin_us, int* shared);
 
 /* replaces SMPL.__init__ (smpl.py:124-275): uploads and re-lays the constants once. */
 int mh_model_create(mh_model** out, const mh_model_host* host);
@@ -175,9 +171,9 @@ int mh_lowest_resolve(const float* verts /*(B,V,3)*/, int B, int V, unsigned lon
 int mh_lbs_set_mode(int split16);
 int mh_lbs_get_mode(void);
 /* mh_lbs_forward_proj as a kernel that is software-pipelined over a wave's vertex tiles (tile i's skinning / projection
- * epilogue issued between the matrix instructions of tile i + 1; on = 1, default), tile after tile (0), or as producer and
- * consumer waves (2: loads and matrix instructions in one wave, epilogue and stores in another, tiles handed over through
- * LDS): the same bits in every form.  MHHIP_FWD_PIPE=0|1|2 in the environment before the first call.  Process-wide.   */
+ * epilogue issued between the matrix instructions of tile i + 1; on = 1, default) or tile after tile (0): the same bits
+ * either way; any other value is an invalid argument.  MHHIP_FWD_PIPE=0 in the environment before the first call selects
+ * 0, any other value 1.  Process-wide.                                                                                */
 int mh_lbs_set_forward_pipeline(int on);
 int mh_lbs_get_forward_pipeline(void);
 

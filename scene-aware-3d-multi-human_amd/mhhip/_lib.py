@@ -139,8 +139,6 @@ def lib():
         L.mh_scene_points.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
         L.mh_stream_create.argtypes = [ctypes.POINTER(vp)]
         L.mh_stream_destroy.argtypes = [vp]
-        L.mh_stream_shares_any.argtypes = [ctypes.POINTER(vp), ctypes.c_int, vp, ctypes.c_float, ctypes.POINTER(ctypes.c_int)]
-        L.mh_streams_classify.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, ctypes.c_float, ctypes.POINTER(ctypes.c_int)]
         L.mh_stream_spin.argtypes = [vp, ctypes.c_float]
         L.mh_streams_share_queue.argtypes = [vp, vp, ctypes.c_float, ctypes.POINTER(ctypes.c_int)]
         L.mh_profile_enable.argtypes = [ctypes.c_int]

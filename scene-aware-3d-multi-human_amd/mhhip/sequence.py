@@ -89,6 +89,7 @@ class SequenceEngine(object):
         self.freeze_xscale = False      # the deferred scale sums are dropped (optim_scale_factor off: the reference zeroes that gradient)
         self._person_now = False
         self._person_pending = False
+        self._leaf_terms_later = False  # the leaf-only terms wait for the side branch (cycle_begin(join=False) -> _finish_a)
         self.ws = model.workspace(B)
         self.ws2 = model.backward_workspace(B)
         self.kp_ws = torch.empty(max(1, _lib.lib().mh_keypoint_workspace_bytes(model.handle, B)), dtype=torch.uint8, device=self.dev)
@@ -380,8 +381,6 @@ class SequenceEngine(object):
                 s['zsnap'][T:].copy_(zh)
         d['ev_snap'].record(side)
         d['snap_pending'] = True
-        if os.environ.get('MHHIP_SCENE_DELAY_US'):      # (probe: the update's wide kernels later in the cycle, DESIGN App. A)
-            check(L.mh_stream_spin(st, float(os.environ['MHHIP_SCENE_DELAY_US'])))
         if 'depths_t' in d:
             check(L.mh_scene_median_t(T, H, W, ptr(d['depths_t']), ptr(d['back_t']), ptr(s['zsnap'][:T]), ptr(s['zsnap'][T:]),
                                       ptr(d['ma_depth']), ptr(d['ma_mask']), ptr(d['ws']), st))
@@ -389,8 +388,6 @@ class SequenceEngine(object):
             check(L.mh_scene_median(T, H, W, ptr(self.depths), ptr(d['back']), ptr(s['zsnap'][:T]), ptr(s['zsnap'][T:]),
                                     ptr(d['ma_depth']), ptr(d['ma_mask']), ptr(d['ws']), st))
         self._scene_finish(s, st)
-        for _ in range(int(os.environ.get('MHHIP_SCENE_DUMMIES', '0') or 0)):      # (probe: what do kernel boundaries on this stream cost the chain?)
-            check(L.mh_stream_spin(st, 0.02))
         s['ev'].record(side)
         d['ready'] = k
         d['next'] = 1 - k
@@ -534,7 +531,7 @@ class SequenceEngine(object):
         ev = self._tic('lbs_forward')
         self._projected_into = None       # one-shot tokens of what this forward's epilogue left behind: consumed by the
         self._lowkey_fresh = False        # rasteriser's preparation (mhhip/raster.py) and by the contact term (_scene_terms)
-        if raster is not None and os.environ.get('MHHIP_NO_PROJ') != '1' and _lib.lib().mh_lbs_get_mode() != 0:
+        if raster is not None and _lib.lib().mh_lbs_get_mode() != 0:
             t = raster.forward_targets()
             if clear is not None:
                 t.clear, t.clear_n = clear.data_ptr(), clear.numel()
@@ -623,19 +620,13 @@ class SequenceEngine(object):
         driver exchanges boundary vertices between this and ``cycle_finish``).  join=False: the leaf-only terms of the side
         branch are NOT waited for here -- the caller's next join covers them (``cycle_graphed``: the one in front of the
         rasteriser's gradient half; its selection half reads nothing they write)."""
-        L = _lib.lib()
-        c = self.c
-        T, N = self.T, self.N
-        g = self.grads
-        log = self.tmp_log
         self._flush_log()                # (never inside a capture: cycle_graphed has flushed before it replays)
         if not torch.cuda.is_current_stream_capturing():
             self._flush_phase()
         # the gradient buffer (+ the staging row of the log) is cleared by the forward's first kernel when the projection form
         # runs (mh_fwd_proj.clear): the captured cycle starts with k_pose_fwd instead of a fill and a 5-us gap
         # (only in the single-join form: with join=True the leaf-only terms start beside the forward and add into the buffer)
-        clear_in_fwd = (not join) and raster is not None and os.environ.get('MHHIP_NO_PROJ') != '1' and os.environ.get('MHHIP_CLEAR_FILL') != '1' \
-            and _lib.lib().mh_lbs_get_mode() != 0
+        clear_in_fwd = (not join) and raster is not None and _lib.lib().mh_lbs_get_mode() != 0
         if not clear_in_fwd:
             self._grads_log.zero_()
         # the terms that only read the leaves (silhouette mask statistics, priors, velocity) run on the second stream
@@ -643,37 +634,47 @@ class SequenceEngine(object):
         main = torch.cuda.current_stream(self.dev)
         side = self._side_stream()
         side.wait_stream(main)
-        s2 = side.cuda_stream
-        pT = self.leaf('poses_T')
-        h = self.halo or {}
         # the chain's kernels are captured BEFORE the side branch's: a replayed graph keeps the branch whose nodes come first
         # on the queue it was launched on and moves the other one to a second queue, and every hop between queues costs
         # 10-14 us of idle time (rocprofv3 trace: the forward used to start 19 us into the cycle, now 9)
         self.forward(regress=False, raster=raster, clear=self._grads_log if clear_in_fwd else None)   # (the per-body pose-prior values are summed with the other log entries, _finish_a)
-        def leaf_terms(part=3):
-            # part: 1 = the silhouette mask statistics (read by the rasteriser's gradient half), 2 = priors + velocity, 3 = both
-            if self.has_images and (part & 1):
-                check(L.mh_sil_mask_stats_cached(ptr(self.bits), T, N, self.H, self.W, ptr(pT), ptr(self.p2d_valid),
-                                                 ptr(self.mask_valid), ptr(self.front), ptr(self.sil_apply), ptr(self.sil_D),
-                                                 ptr(self.sil_S), ptr(self.sil_tag), s2))
-            if not (part & 2):
-                return
-            check(L.mh_prior_terms(T, N, self.nbatches, ptr(self.leaf('poses_smpl')), ptr(self.poses_ref), ptr(self.valid),
-                                   ptr(self.leaf('betas')), ptr(self.betas_ref), ptr(self.leaf('xscale')),
-                                   float(c['reg_poses']), float(c['reg_scales']), ptr(self.leaf('poses_smpl', g)),
-                                   ptr(self.leaf('betas', g)), ptr(self.leaf('xscale', g)), ptr(self.prior_body), ptr(log[9:12]), s2))
-            check(L.mh_velocity_term(T, N, ptr(pT), ptr(h.get('pT_prev')), ptr(h.get('pT_next')), float(c['reg_velocity']),
-                                     ptr(self.leaf('poses_T', g)), ptr(log[7:8]), s2))
-
-        # without a join here nothing needs these terms before the side branch ends: they are launched at its END then
+        # without a join here nothing needs these terms before the side branch ends: they are launched in it then
         # (_finish_a), so that the vertex-dependent kernels start right behind the forward instead of 50 us later
-        self._leaf_terms_later = None
-        if not join:
-            self._leaf_terms_later = leaf_terms
-        else:
-            leaf_terms()
+        self._leaf_terms_later = not join
         if join:
+            self._leaf_terms(side.cuda_stream)
             main.wait_stream(side)
+
+    def _leaf_terms(self, st):
+        """the silhouette mask statistics (read by the rasteriser's gradient half), priors and velocity on stream st"""
+        L, c = _lib.lib(), self.c
+        T, N = self.T, self.N
+        g, log = self.grads, self.tmp_log
+        pT = self.leaf('poses_T')
+        h = self.halo or {}
+        if self.has_images:
+            check(L.mh_sil_mask_stats_cached(ptr(self.bits), T, N, self.H, self.W, ptr(pT), ptr(self.p2d_valid),
+                                             ptr(self.mask_valid), ptr(self.front), ptr(self.sil_apply), ptr(self.sil_D),
+                                             ptr(self.sil_S), ptr(self.sil_tag), st))
+        check(L.mh_prior_terms(T, N, self.nbatches, ptr(self.leaf('poses_smpl')), ptr(self.poses_ref), ptr(self.valid),
+                               ptr(self.leaf('betas')), ptr(self.betas_ref), ptr(self.leaf('xscale')),
+                               float(c['reg_poses']), float(c['reg_scales']), ptr(self.leaf('poses_smpl', g)),
+                               ptr(self.leaf('betas', g)), ptr(self.leaf('xscale', g)), ptr(self.prior_body), ptr(log[9:12]), st))
+        check(L.mh_velocity_term(T, N, ptr(pT), ptr(h.get('pT_prev')), ptr(h.get('pT_next')), float(c['reg_velocity']),
+                                 ptr(self.leaf('poses_T', g)), ptr(log[7:8]), st))
+
+    def _regress_project(self, st):
+        """the 17 key-points of the 2D term: value, projection, residual and adjoint on stream st"""
+        if self.kp_fused:
+            self.keypoint_terms(st)
+            return
+        jwp = None if self.joint_w is None else self.joint_w.ctypes.data_as(_lib.c_float_p)
+        Kp = self.K.ctypes.data_as(_lib.c_float_p)
+        Kdp = None if self.Kd is None else self.Kd.ctypes.data_as(_lib.c_float_p)
+        self._kp_chunk = False
+        self._regress(st)
+        check(_lib.lib().mh_project_joints_loss_w(self.B, ptr(self.kp), Kp, Kdp, jwp, ptr(self.pose2d), self.thr, 0, float(self.W),
+                                                  float(self.H), float(self.c['proj2d']), ptr(self.uv), ptr(self.gj), ptr(self.loss2d), st))
 
     def cycle_finish(self, row, use_images=True, raster=None, scene_ready=False):
         self._finish_a(use_images, raster, scene_ready=scene_ready)
@@ -692,8 +693,6 @@ class SequenceEngine(object):
         st = main.cuda_stream
         c = self.c
         T, N, B = self.T, self.N, self.B
-        Kp = self.K.ctypes.data_as(_lib.c_float_p)
-        Kdp = None if self.Kd is None else self.Kd.ctypes.data_as(_lib.c_float_p)
         h = self.halo or {}
         # sel: the device-built scene sets, read through the device-resident selector (gated launches: they run -- and do
         # nothing -- while there is no scene yet, so that the captured sequence is the same before and after cycle 30)
@@ -719,35 +718,17 @@ class SequenceEngine(object):
         side.wait_stream(main)
         s2 = side.cuda_stream
 
-        def regress_project():
-            if self.kp_fused and os.environ.get('MHHIP_NO_KPALG') != '1':
-                self.keypoint_terms(s2)
-                return
-            jwp = None if self.joint_w is None else self.joint_w.ctypes.data_as(_lib.c_float_p)
-            self._kp_chunk = False
-            self._regress(s2)
-            check(L.mh_project_joints_loss_w(B, ptr(self.kp), Kp, Kdp, jwp, ptr(self.pose2d), self.thr, 0, float(self.W),
-                                             float(self.H), float(c['proj2d']), ptr(self.uv), ptr(self.gj), ptr(self.loss2d), s2))
-
         def side_branch():
-            # order (same-box A/B with the chain on the launch queue): the vertex-gradient initialisation first -- 200 MB beside
-            # the rasteriser's preparation, which is bound by latency -- then the key-point terms, the contact chain and, when
-            # the caller left them to this branch, the leaf-only terms: everything behind the initialisation lands under
-            # the selection kernel.  (With the side branch on the launch queue, round 2, the regression had to come first.)
-            # round 4: the key-point launches (operands in L2) and the leaf-only terms go FIRST -- small kernels beside the
-            # rasteriser's preparation -- and the 200 MB of the vertex-gradient initialisation behind them: beside it the
-            # one-workgroup list kernel of the preparation took 38 us instead of 11 (0.719 -> 0.711 ms same-box)
-            order_old = os.environ.get('MHHIP_SIDE_ORDER') == '0'
-            fv_first = self.kp_fused and order_old
-            later = getattr(self, '_leaf_terms_later', None)
-            self._leaf_terms_later = None
-            # (a second side branch under the gradient half and the skinning adjoint -- key-point launches, priors, velocity --
-            # was tried in round 5, MHHIP_SIDE_SPLIT: +45 us; DESIGN App. A)
-            if not fv_first:
-                regress_project()
-                if later is not None and not order_old:
-                    later(3)
-                    later = None
+            # order (round 4): the key-point launches (operands in L2) and, when the caller left them to this branch, the
+            # leaf-only terms FIRST -- small kernels beside the rasteriser's preparation -- and the 200 MB of the vertex-gradient
+            # initialisation behind them: beside it the one-workgroup list kernel of the preparation took 38 us instead of 11
+            # (0.719 -> 0.711 ms same-box).  Then the contact chain: everything behind the initialisation lands under the
+            # selection kernel.  (A second side branch under the gradient half and the skinning adjoint -- key-point launches,
+            # priors, velocity -- was tried in round 5: +45 us; DESIGN App. A)
+            self._regress_project(s2)
+            if self._leaf_terms_later:
+                self._leaf_terms_later = False
+                self._leaf_terms(s2)
             with torch.cuda.stream(side):
                 if need_gv and filt and h.get('poses') is not None:
                     self._halo_forward(h, s2)
@@ -775,16 +756,12 @@ class SequenceEngine(object):
                 if not hasattr(self, '_ev_gv'):
                     self._ev_gv = torch.cuda.Event()
                 self._ev_gv.record(side)
-            if fv_first:
-                regress_project()
             self._scene_done = False
             sums = [(self.loss2d, log[0:1]), (self.prior_body, log[3:4])]
             if scene and (self._scene_dev is None or scene_ready):     # static scene, or its event already waited for
                 self._scene_terms(s2, reduce=False, sel=sel)
                 sums += [(self.batch_contact, log[5:6]), (self.batch_foot, log[6:7])]
                 self._scene_done = True
-            if later is not None:
-                later()
             _lib.reduce_sum_multi(sums, s2)                            # the small log sums of the side branch: one launch
         # ---- main branch: rasterised depth / silhouette terms ----------------------------------------------------------
         joined = False
@@ -800,10 +777,8 @@ class SequenceEngine(object):
                 # the rasteriser's work lists (a schedule) are rebuilt beside the LBS backward, for the NEXT cycle, when the
                 # backward is the fused form that carries the closing job (one launch and 16 us less between the forward and
                 # the selection kernel); the kernels find every tile with lists that are a cycle old
-                ldef = 128 if (self.kp_fused and os.environ.get('MHHIP_NO_KPALG') != '1' and os.environ.get('MHHIP_NO_DEFER') != '1'
-                               and os.environ.get('MHHIP_LISTS_ONCHAIN') != '1') else 0
-                side_late = os.environ.get('MHHIP_SIDE_LATE', '1' if ldef else '0') == '1'
-                if main_first and side_late:
+                ldef = 128 if self.kp_fused and os.environ.get('MHHIP_NO_DEFER') != '1' else 0
+                if ldef:
                     # The side branch opens BEHIND the rasteriser's preparation, with the selection kernel already launched.
                     # With the work lists on the chain (two small launches between the forward and the selection) this order
                     # loses (r04: 0.750 ms against 0.735: the side branch starts 20 us later and ends under the selection
@@ -815,11 +790,9 @@ class SequenceEngine(object):
                     raster(self, gv, log, phases=4 | ldef)
                     side.wait_stream(main)
                     raster(self, gv, log, phases=8)
-                    side_branch()
                 else:
-                    raster(self, gv, log, phases=(4 | 8 | ldef) if ldef else 1)
-                    if main_first:
-                        side_branch()
+                    raster(self, gv, log, phases=1)
+                side_branch()
                 # the whole side branch ends long before the selection does: ONE join here instead of a wait for the
                 # buffer initialisation here and a second join in front of the backward (every cross-stream edge of
                 # the replayed graph costs several us of idle time on the chain, even when its event has long been
@@ -992,15 +965,7 @@ class SequenceEngine(object):
         """Run ``fn`` (a fixed launch sequence on static buffers) through a captured graph; the first
         call runs it eagerly (lazy allocations, one-time attribute calls) and captures it."""
         if wait_scene and self._scene_pending:   # cross-stream dependency stays outside the captured sequence
-            main = torch.cuda.current_stream(self.dev)
-            if os.environ.get('MHHIP_GATE_PROBE') == '1':      # (probe: how long does the cycle wait for the previous scene update?)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(main)
-                main.wait_event(self._scene_event)
-                e1.record(main)
-                self.__dict__.setdefault('_gate_probe', []).append((e0, e1))
-            else:
-                main.wait_event(self._scene_event)
+            torch.cuda.current_stream(self.dev).wait_event(self._scene_event)
             self._scene_pending = False
         if not hasattr(self, '_graphs'):
             self._graphs = {}
@@ -1017,7 +982,7 @@ class SequenceEngine(object):
         else:
             # a new graph that runs beside the device-side scene update: its first replays also find out which hardware queues
             # it keeps busy, and the scene update moves to one it does not (mhhip/queues.py)
-            want = self._scene_dev is not None and queues.enabled() and str(key[0]).startswith('full') and os.environ.get('MHHIP_LANE_TEST') != '0'      # (the cycle's graphs only)
+            want = self._scene_dev is not None and queues.enabled() and str(key[0]).startswith('full')      # (the cycle's graphs only)
             lt = self._lane_tests.get(key) if want else None
             if lt is None and want and key not in self._lane_tests:
                 lt = self._lane_tests[key] = queues.LaneTest(queues.plan(self.dev), torch.cuda.current_stream(self.dev).cuda_stream)
@@ -1040,39 +1005,35 @@ class SequenceEngine(object):
         device-side scene update (``scene_device_update``), after the first replay has been enqueued."""
         self._flush_person()
         self._person_now = bool(self.defer_person) and os.environ.get('MHHIP_DEFER_PERSON') != '0'
-        key = self._graph_key(raster) + (self._person_now,)
-        self._flush_log()
-        self._flush_phase()
-        if scene_update and queues.enabled() and os.environ.get('MHHIP_LANE_PICK') != '0':
-            self._scene_pick(key)
-        if scene_update:
-            self.scene_device_mark()
-        if self._scene_dev is not None:
+        try:
+            key = self._graph_key(raster) + (self._person_now,)
+            self._flush_log()
+            self._flush_phase()
+            if scene_update and queues.enabled():
+                self._scene_pick(key)
+            if scene_update:
+                self.scene_device_mark()
             # The scene cloud is rebuilt every cycle on its own stream; the update this cycle's contact term reads was
             # launched a whole cycle ago (and takes less than half of one), so the wait for its event is hoisted to the
             # start of the cycle (replay() issues it in front of the graph: it never stalls in practice) and the cycle
             # stays ONE graph with the contact chain in the side branch, hidden under the selection kernel as with a
             # static scene.  (Until late in round 2 the cycle was split in two graphs at the contact chain: a graph
             # boundary of ~30 us and the chain on the critical path.)
-            def body_org():
-                nj = raster is not None and self.has_images
-                self.cycle_begin(join=not nj, raster=raster if self.has_images else None)
-                self.cycle_finish(None, raster=raster, scene_ready=True)
-            self.replay(('full+scene',) + key, body_org)
-            if scene_update:
-                self.scene_device_launch()
-        else:
+            scene_ready = self._scene_dev is not None
+
             def body():
                 # nothing of the rasteriser's selection half reads what the leaf-only terms of the side branch write: with
                 # gradients asked for, the one join in front of the gradient half covers them
                 nj = raster is not None and self.has_images
                 self.cycle_begin(join=not nj, raster=raster if self.has_images else None)
-                self.cycle_finish(None, raster=raster)
-            self.replay(('full',) + key, body)
+                self.cycle_finish(None, raster=raster, scene_ready=scene_ready)
+            self.replay(('full+scene' if scene_ready else 'full',) + key, body)
             if scene_update:
                 self.scene_device_launch()
-        self._log_pending = row            # copied by the next step() (same launch) or by whoever reads the log first
-        self._person_pending, self._person_now = self._person_now, False
+            self._log_pending = row        # copied by the next step() (same launch) or by whoever reads the log first
+            self._person_pending = self._person_now
+        finally:
+            self._person_now = False       # (also when a capture or a replay raises)
 
     def step_dev(self, alpha=0.5, momentum=0.9, eps=1e-8, gamma=0.99, lr0=0.01):
         if not hasattr(self, 'lr_dev'):

@@ -1,8 +1,6 @@
 """developer tool (GPU box): stand-alone time of the "LBS + projection" forward at C3 (k_pose_fwd + the skinning kernel, eager
 launches with events around them) for each form of the kernel: mh_lbs_set_forward_pipeline 0 (tile after tile) / 1 (software
-pipeline over a wave's tiles) / 2 (producer and consumer waves).  python tools/fwd_probe.py [modes [dbg [tiles per workgroup]]]
-(the dbg column drove the timing-only variants of the producer / consumer kernel while they existed: csrc/mh_lbs.hip has
-their numbers)"""
+pipeline over a wave's tiles).  python tools/fwd_probe.py [modes]"""
 import os, sys, tempfile
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,16 +36,8 @@ def timed(n=40):
     return float(np.median(ts)), float(np.min(ts))
 
 
-modes = [int(x) for x in (sys.argv[1] if len(sys.argv) > 1 else '0,1,2').split(',')]
-dbgs = [int(x) for x in (sys.argv[2] if len(sys.argv) > 2 else '0').split(',')]
+modes = [int(x) for x in (sys.argv[1] if len(sys.argv) > 1 else '0,1').split(',')]
 for m in modes:
     _lib.check(L.mh_lbs_set_forward_pipeline(m))
-    for d in (dbgs if m == 2 else [0]):
-        os.environ['MHHIP_FWDPC_DBG'] = str(d)
-        for tpb in ([None] if len(sys.argv) <= 3 else [int(x) for x in sys.argv[3].split(',')]):
-            if tpb is None:
-                os.environ.pop('MHHIP_FWD_TPB', None)
-            else:
-                os.environ['MHHIP_FWD_TPB'] = str(tpb)
-            med, mn = timed()
-            print('pipe %d dbg %d tpb %s: forward (pose + skinning) median %.1f us, min %.1f us' % (m, d, tpb, med, mn), flush=True)
+    med, mn = timed()
+    print('pipe %d: forward (pose + skinning) median %.1f us, min %.1f us' % (m, med, mn), flush=True)
