@@ -645,6 +645,38 @@ int mh_raster_get_winners(void);
 int mh_raster_set_deterministic(int on);
 int mh_raster_get_deterministic(void);
 
+/* ---- the fitted scene as images: composite over the people of every frame ----------------------
+ * Replaces the reference's look at a result -- matplotlib scatter plots of the projected vertices
+ * (predict.py:195-243) -- with images computed where the fit ran.
+ * ws: a rasteriser workspace on which a selection pass (phases & 1 of mh_raster_terms*) for exactly
+ * these T,N,V,F,H,W has run: per body a screen window and, per window pixel, the nearest face
+ * (z bits << 32 | face; mh_raster_workspace_offsets).  Read only.  N <= 32.
+ * In : verts (T*N,V,3) camera space, the vertices of that pass; faces (F,3); images (T,H,W,3) u8 or
+ *      NULL (= black); palette (N,3) DEVICE, in [0,1]; light HOST [3], unit, camera space: the
+ *      direction the light TRAVELS -- shade = ambient + (1 - ambient) * max(0, -n.light), n the
+ *      normal below: (0,0,1) is a head-light; (0,0,-1) shines at the camera from behind the scene
+ *      and leaves every pixel at the ambient term (flat colours); ambient, alpha in [0,1].
+ * Out (each may be NULL = skipped; all NULL is an error), per pixel of frame t:
+ *   winner  = among the bodies n whose window holds the pixel and whose nearest-face key is not
+ *             empty, the smallest (z, n): z compared as the float the key stores, the lower person
+ *             index wins an exact tie;
+ *   depth   (T,H,W)   the winner's z -- for an unoccluded body the same bits zbuf_out reports; -1 = empty;
+ *   person, face (T,H,W) the winner's n and face index; -1 = empty;
+ *   normal  (T,H,W,3) unit geometric normal (v1-v0)x(v2-v0) of the winning face from `verts`, flipped
+ *             so that n_z <= 0 (towards the camera); 0 where the pixel is empty or the product is 0;
+ *   overlay (T,H,W,3) u8 round(clamp((1-alpha) img + alpha c, 0, 255)), c = 255 palette[person] shade;
+ *             empty pixels copy img;
+ *   visible (T,N,V) u8 = 1 for the three vertices of every face that owns at least one pixel; the
+ *             CALLER passes it zeroed.  Pixel-sampled visibility: it depends on the resolution (a
+ *             face that falls between the pixel centres is not seen);
+ *   coverage (T,N) i32 pixels every person owns (zeroed here; integer sums, exact in any order).     */
+int mh_scene_composite(int T, int N, int V, int F, int H, int W,
+                       const float* verts, const int32_t* faces, const void* ws,
+                       const uint8_t* images, const float* palette, const float* light /*HOST [3]*/,
+                       float ambient, float alpha,
+                       float* depth, int32_t* person, int32_t* face, float* normal,
+                       uint8_t* overlay, uint8_t* visible, int32_t* coverage, void* stream);
+
 /* ---- stand-alone forms of losses.py:19-40 and morphology.py:6-41 (call compatibility of
  * mhmocap.losses / mhmocap.morphology; the optimiser uses the fused kernels above) --------------
  * mh_avg_depth_loss: rows = b*N maps of P pixels; `tru` has rows/group maps (group = N when the

@@ -181,6 +181,7 @@ def lib():
             ctypes.c_int, vp, vp, ctypes.c_int, ctypes.POINTER(RasterFin), vp]
         L.mh_raster_workspace_init.argtypes = [ctypes.c_int] * 6 + [vp, vp]
         L.mh_raster_workspace_offsets.argtypes = [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_size_t)]
+        L.mh_scene_composite.argtypes = [ctypes.c_int] * 6 + [vp] * 5 + [c_float_p, ctypes.c_float, ctypes.c_float] + [vp] * 8
         L.mh_avg_depth_loss.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, vp, vp, vp]
         L.mh_avg_depth_loss_backward.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, vp, ctypes.c_float, vp, vp, vp]
         L.mh_masked_mse.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, vp]

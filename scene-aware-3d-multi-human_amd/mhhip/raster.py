@@ -158,3 +158,83 @@ def render(model, verts, cam_K, image_size):
                                      ptr(tz), ptr(ones), ptr(tz), 0.0, 0.0, 1e-3, None, None, None, ptr(zf(B)), ptr(zf(B)),
                                      ptr(ws), ptr(zbuf), ptr(alpha), _lib.stream_ptr(dev)))
     return zbuf, alpha
+
+
+SCENE_OUTPUTS = ('depth', 'person', 'face', 'normal', 'overlay', 'visible', 'coverage')
+
+
+def default_palette(num_people):
+    """The colour of person n, whatever the number of people: hue = frac(n * 0.61803398875) (golden-ratio steps, first
+    person at hue 0), saturation 0.65, value 0.95, HSV -> RGB; (num_people, 3) float32 in [0, 1]."""
+    import colorsys
+    return np.asarray([colorsys.hsv_to_rgb((n * 0.61803398875) % 1.0, 0.65, 0.95) for n in range(int(num_people))],
+                      np.float32).reshape(-1, 3)
+
+
+def render_scene(model, verts, cam_K, image_size, images=None, palette=None, light=(0, 0, -1), ambient=0.3, alpha=0.6,
+                 outputs=None, chunk=32):
+    """The fitted scene as images (``mh_scene_composite``): verts (T,N,V,3) on the device, camera space -> dict of device
+    tensors, every one composited over the N people of a frame by the nearest z (the lower person index wins a tie):
+
+    depth (T,H,W) f32 (-1 = empty) | person, face (T,H,W) i32 (-1 = empty) | normal (T,H,W,3) f32, unit geometric normal
+    of the winning face with n_z <= 0 | overlay (T,H,W,3) u8: the person's colour, shaded, blended with weight ``alpha``
+    over ``images`` ((T,H,W,3) u8, None = black) | visible (T,N,V) u8: vertices of the faces that own a pixel (pixel-sampled:
+    depends on the resolution) | coverage (T,N) i32: pixels every person owns.
+
+    ``palette`` (N,3) in [0,1], default ``default_palette(N)``; ``light``: unit direction the light travels in camera
+    space, shade = ambient + (1 - ambient) max(0, -n.light) -- (0,0,1) is a head-light, the default (0,0,-1) leaves the
+    flat ambient colours; ``outputs``: names of the outputs wanted (default all), only those are allocated and returned.
+    The selection pass runs like in ``render`` (loss coefficients 0, no gradients) over at most ``chunk`` frames at a time
+    on one workspace of its own, so memory beyond the outputs does not grow with T."""
+    W, H = int(image_size[0]), int(image_size[1])
+    if verts.dim() != 4 or verts.shape[-1] != 3:
+        raise ValueError('verts must be (T,N,V,3), got %s' % (tuple(verts.shape),))
+    T, N, V = int(verts.shape[0]), int(verts.shape[1]), int(verts.shape[2])
+    names = SCENE_OUTPUTS if outputs is None else tuple(outputs)
+    bad = [k for k in names if k not in SCENE_OUTPUTS]
+    if bad or not names:
+        raise ValueError('outputs must name some of %s, got %r' % (', '.join(SCENE_OUTPUTS), outputs))
+    if N > 32:
+        raise ValueError('at most 32 people per frame, got %d' % N)
+    chunk = max(1, min(int(chunk), T))
+    dev = verts.device
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        st = _lib.stream_ptr(dev)
+        verts = verts.contiguous().float()
+        faces = torch.as_tensor(np.ascontiguousarray(np.asarray(model.faces).astype(np.int32))).to(dev)
+        F = int(faces.shape[0])
+        if images is not None:
+            images = torch.as_tensor(images).to(dev).contiguous()
+            if images.dtype != torch.uint8 or tuple(images.shape) != (T, H, W, 3):
+                raise ValueError('images must be (T,H,W,3) uint8 = (%d,%d,%d,3), got %s %s' % (T, H, W, images.dtype, tuple(images.shape)))
+        pal = default_palette(N) if palette is None else np.ascontiguousarray(np.asarray(palette, np.float32))
+        if pal.shape != (N, 3):
+            raise ValueError('palette must be (N,3) = (%d,3), got %s' % (N, pal.shape))
+        pal = torch.as_tensor(pal).to(dev)
+        lgt = np.ascontiguousarray(np.asarray(light, np.float32).reshape(3))
+        shapes = dict(depth=((T, H, W), torch.float32), person=((T, H, W), torch.int32), face=((T, H, W), torch.int32),
+                      normal=((T, H, W, 3), torch.float32), overlay=((T, H, W, 3), torch.uint8), visible=((T, N, V), torch.uint8),
+                      coverage=((T, N), torch.int32))
+        out = {k: (torch.zeros if k == 'visible' else torch.empty)(shapes[k][0], dtype=shapes[k][1], device=dev) for k in names}
+        # the inputs of the rasterised terms, all zero: only the windows and keys of the selection pass are wanted
+        zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+        zf = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        bits, depths, tz, zb, ones = zi(chunk, H, W), zf(chunk, H, W), zf(chunk), zf(chunk * N), torch.ones(chunk * N, device=dev)
+        front, dbody, sbody = zi(chunk * N), zf(chunk * N), zf(chunk * N)
+        K = np.ascontiguousarray(np.asarray(cam_K, np.float32).reshape(9))
+        ws = torch.empty(L.mh_raster_workspace_bytes(chunk, N, V, F, H, W), dtype=torch.uint8, device=dev)
+        for t0 in range(0, T, chunk):
+            tc = min(chunk, T - t0)
+            dims = (tc, N, V, F, H, W)
+            v = verts[t0:t0 + tc]
+            # a fresh workspace for every chunk (its layout follows the frame count): no face list of other frames is kept
+            check(L.mh_raster_workspace_init(*dims, ptr(ws), st))
+            check(L.mh_raster_terms_phase(*dims, K.ctypes.data_as(_lib.c_float_p), ptr(v), ptr(faces), ptr(bits), ptr(bits),
+                                          ptr(depths), ptr(tz), ptr(tz), ptr(ones), ptr(front), ptr(zb), ptr(ones), ptr(zb),
+                                          0.0, 0.0, 1e-3, None, None, None, ptr(dbody), ptr(sbody), ptr(ws), None, None, 1, st))
+            o = lambda k: ptr(out[k][t0:t0 + tc]) if k in out else None
+            check(L.mh_scene_composite(*dims, ptr(v), ptr(faces), ptr(ws), None if images is None else ptr(images[t0:t0 + tc]),
+                                       ptr(pal), lgt.ctypes.data_as(_lib.c_float_p), float(ambient), float(alpha), o('depth'),
+                                       o('person'), o('face'), o('normal'), o('overlay'), o('visible'), o('coverage'), st))
+    return out

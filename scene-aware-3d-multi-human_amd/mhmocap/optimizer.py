@@ -649,6 +649,50 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
             'scene_mask': self.scene_mask if hasattr(self, 'scene_mask') else None,
         }
 
+    # -- the fit as images (the reference looks at it with scatter plots of projected vertices, predict.py:195-243) ------
+    def render_scene(self, frames=None, images=True, **kw):
+        """Render the current leaves at ``frames`` (default: all): the vertices of ``predict`` (LBS, scale, translation)
+        composited over the people of every frame by ``mhhip.raster.render_scene`` -- depth, person and face labels,
+        normals, a shaded overlay on the staged input images (``images=True`` and images were staged; else on black),
+        vertex visibility and per-person pixel counts, as numpy arrays, plus ``'frames'``.  ``kw`` goes to
+        ``mhhip.raster.render_scene`` (palette, light, ambient, alpha, outputs, chunk).  Reads the leaves only: buffers
+        and rasteriser workspace of its own, nothing of the engine's state is written."""
+        from mhhip import raster
+        if self.engine is None:
+            raise RuntimeError('render_scene: nothing to render before init_optimized_variables()')
+        if self._world()[0] > 1:
+            raise RuntimeError('render_scene is not available in a frame-sharded run (world > 1): render from the gathered '
+                               'result of get_optimized_variables() in one process')
+        e = self.engine
+        T, N = self.num_frames, self.num_people
+        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
+        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
+            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
+        idx = idx.astype(np.int64)
+        imgs = None
+        if images and getattr(self, '_staged', False) and getattr(self, '_images', None) is not None:
+            imgs = np.asarray(self._images)
+            if imgs.shape != (T, self.img_h, self.img_w, 3):
+                raise ValueError('staged images are %s, not (T,H,W,3) = (%d,%d,%d,3)' % (imgs.shape, T, self.img_h, self.img_w))
+            imgs = np.ascontiguousarray(imgs[idx]).astype(np.uint8)
+        chunk = max(1, int(kw.pop('chunk', 32)))
+        sel = torch.as_tensor(idx, device=self.device)
+        with torch.cuda.device(self.device), torch.no_grad():
+            pT = e.leaf('poses_T').view(T, N, 3)[sel]
+            pose = e.leaf('poses_smpl').view(T, N, 72)[sel]
+            parts = []
+            for f0 in range(0, len(idx), chunk):
+                sl = slice(f0, min(len(idx), f0 + chunk))
+                nb = (sl.stop - sl.start) * N
+                verts, _, _, _ = self.SMPLPY.body_model.lbs_forward(e.leaf('betas').view(N, 10), pose[sl].reshape(nb, 72),
+                                                                    e.leaf('xscale').view(N), pT[sl].reshape(nb, 3), want_vposed=False)
+                got = raster.render_scene(self.SMPLPY.body_model, verts.view(sl.stop - sl.start, N, -1, 3), self.cam_K,
+                                          (self.img_w, self.img_h), images=None if imgs is None else imgs[sl], chunk=chunk, **kw)
+                parts.append({k: v.cpu().numpy() for k, v in got.items()})
+        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+        out['frames'] = idx
+        return out
+
     # -- reference optimizer.py:664-675 ---------------------------------------------------------------
     def one_euro_filter(self, x, min_cutoff=0.1, beta=0.02, frame_rate=25):
         x = torch.as_tensor(x).detach().to(self.device).float()
