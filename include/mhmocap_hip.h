@@ -677,6 +677,57 @@ int mh_scene_composite(int T, int N, int V, int F, int H, int W,
                        float* depth, int32_t* person, int32_t* face, float* normal,
                        uint8_t* overlay, uint8_t* visible, int32_t* coverage, void* stream);
 
+/* ---- the fit in numbers: per frame and per person, computed where the fit ran ---------------------
+ * Replaces paging through the images above (and the reference's scatter plots, predict.py:141-257)
+ * when the question is WHICH of T x N bodies went wrong.  Both calls are read-only on their inputs,
+ * zero their outputs themselves and check their arguments before any HIP call.
+ *
+ * mh_fit_report_pixels: one pass over the pixels of T frames, N <= 32 people.
+ * In : person, depth (T,H,W) as mh_scene_composite wrote them (-1 = empty); bits (T,H,W) of
+ *      mh_pack_masks, read as UNSIGNED words (person 31 is bit 31), bits >= N and labels outside
+ *      [0,N) are ignored; disp (T,H,W) the staged normalised disparity with min_z, max_z (T) DEVICE,
+ *      the activations of the depth-range leaves -- all three NULL: no depth sums; scene_depth (H,W)
+ *      f32 and scene_mask (H,W) u8 -- both NULL: no scene.
+ * Out (one of the two may be NULL), for frame t and person n:
+ *   counts[t][n] = { rendered:     pixels with person == n,
+ *                    segmented:    pixels whose word has bit n set,
+ *                    intersection: pixels with both,
+ *                    behind:       pixels with person == n, scene_mask != 0 and
+ *                                  depth > scene_depth + margin (ONE float add, then the compare);
+ *                                  0 without a scene };
+ *   dsum[t][n]   = { sum d, sum |d| } over the intersection pixels,
+ *                  d = depth + depth_offset - 1 / (disp (1/min_z[t] - 1/max_z[t]) + 1/max_z[t]):
+ *                  rendered against target depth in metres (optimizer.py:425; depth_offset is the
+ *                  0.2 of optimizer.py:440, passed by the caller); both 0 without disp.
+ * The counts are integer sums, exact in any order.  The two float sums have the same bits on every
+ * launch: every d is evaluated in float32, clamped to +-1e9 (NaN counts as -1e9) and added as a
+ * 64-BIT FIXED-POINT INTEGER of 2^-28 m (3.7e-9 m; sums up to 3.4e10 m) -- integer atomics in LDS
+ * and one integer atomic per workgroup, person and sum in device memory, exact in any order -- and
+ * the total is rounded to float32 once.  No float atomics.  The accumulators (16 T N bytes) are
+ * obtained from and returned to the stream's memory pool (hipMallocAsync) inside the call; on a
+ * device without a pool they are a plain allocation and the call waits for the stream before freeing.
+ * The grid is sized by T H W, not by T: about 2048 workgroups whether T is 1 or 2000.
+ *
+ * mh_fit_report_verts: body against scene, one pass over the vertices of B bodies.  K: HOST 3x3.
+ * A vertex (x,y,z) of camera space with z > 0 falls into pixel (floor(u), floor(v)),
+ * u = fx x / z + cx, v = fy y / z + cy (pixel centres at +0.5: the inverse of mh_scene_unproject).
+ * It is skipped when z <= 0, when the pixel is outside the image or when scene_mask is 0 there, and
+ * it is INSIDE the scene when z - scene_depth[pixel] > margin (margin >= 0).
+ *   pen_count[b] = number of such vertices; pen_max[b] = the largest z - scene_depth[pixel] among
+ *   them, 0 if there are none (a maximum over the bit patterns of positive floats: exact in any order).
+ * Unlike the `behind` count above this sees vertices hidden by another person or by the body itself.
+ * One of the two outputs may be NULL.                                                              */
+int mh_fit_report_pixels(int T, int N, int H, int W,
+                         const int32_t* person, const float* depth, const uint32_t* bits,
+                         const float* disp, const float* min_z, const float* max_z,
+                         const float* scene_depth, const uint8_t* scene_mask,
+                         float depth_offset, float margin,
+                         int32_t* counts /*(T,N,4)*/, float* dsum /*(T,N,2)*/, void* stream);
+int mh_fit_report_verts(int B, int V, int H, int W, const float* K /*HOST 3x3*/,
+                        const float* verts /*(B,V,3)*/, const float* scene_depth /*(H,W)*/,
+                        const uint8_t* scene_mask /*(H,W)*/, float margin,
+                        int32_t* pen_count /*(B)*/, float* pen_max /*(B)*/, void* stream);
+
 /* ---- stand-alone forms of losses.py:19-40 and morphology.py:6-41 (call compatibility of
  * mhmocap.losses / mhmocap.morphology; the optimiser uses the fused kernels above) --------------
  * mh_avg_depth_loss: rows = b*N maps of P pixels; `tru` has rows/group maps (group = N when the

@@ -240,6 +240,7 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         self._global_leaves()                     # sharded: gathered once here, served locally until fit() ends
         self.scene_depth = None
         self.scene_pcd = None
+        self._report_scene = None
         self.poses_T_filtered = None
         self.verts_filtered = None
         return init_log
@@ -617,6 +618,7 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
             return
         self.scene_depth, ma_mask, pts = e.scene_device_result()
         self.scene_pcd = pts.unsqueeze(0).unsqueeze(0)
+        self._report_scene = (self.scene_depth, ma_mask)
         if self._images is not None:
             # colour median + looped 11x11 fill on the device (independent of the optimised variables: once per fit);
             # frame-sharded: pixel-sharded over the ranks like the depth median
@@ -626,6 +628,8 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
     def update_scene_pointcloud(self, scene_depth, scene_mask):
         pts = self.engine.scene_from_depth(np.asarray(scene_depth, np.float32), np.asarray(scene_mask))
         self.scene_pcd = pts.unsqueeze(0).unsqueeze(0)                        # (1,1,M,3)
+        # the maps the cloud came from, for fit_report (body against scene is measured per pixel of the depth map)
+        self._report_scene = (np.array(scene_depth, np.float32), np.asarray(scene_mask, np.float32) > 0.5)
 
     # -- reference optimizer.py:619-636 ---------------------------------------------------------------
     def get_optimized_variables(self):
@@ -690,6 +694,74 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
                                           (self.img_w, self.img_h), images=None if imgs is None else imgs[sl], chunk=chunk, **kw)
                 parts.append({k: v.cpu().numpy() for k, v in got.items()})
         out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+        out['frames'] = idx
+        return out
+
+    # -- the fit in numbers (the reference has scatter plots to look at, predict.py:141-257) -----------------------------
+    def fit_report(self, frames=None, margin=0.05, chunk=32):
+        """Per frame and per person, how well the current leaves fit at ``frames`` (default: all): dict of numpy arrays of
+        shape (len(frames), N) -- the columns of ``mhhip.report.fit_report`` (reproj_px, reproj_max_px, joints_used,
+        mask_rendered, mask_seg, mask_inter, mask_iou, depth_bias_m, depth_abs_m, behind_scene_px, pen_verts, pen_max_m,
+        contact_dy_m, foot_slide_m) and ``valid`` (``valid_smpl`` of the inputs, thresholded as the fit does) -- plus
+        ``'frames'``.  The scene is the depth map and mask the last ``update_scene_pointcloud`` was handed or the last fit's
+        scene update left (``scene_depth`` with the mask of its point cloud; else ``scene_depth`` / ``scene_mask``) with the
+        cloud ``scene_pcd``; without one the scene columns are -1 (counts) / NaN.  Without staged images (no fit yet, or a
+        dataloader without masks and depths) the mask and depth columns are -1 / NaN.  ``min_z`` / ``max_z`` are those of
+        ``get_optimized_variables``; ``foot_slide_m`` pairs frame t with frame t - 1 of the SEQUENCE (NaN for frame 0), whose
+        forward is computed when it is not among ``frames``.  At most ``chunk`` frames are on the device at a time.  Reads
+        the leaves only: buffers and rasteriser workspace of its own, nothing of the engine's state is written."""
+        from mhhip import report
+        if self.engine is None:
+            raise RuntimeError('fit_report: nothing to report before init_optimized_variables()')
+        if self._world()[0] > 1:
+            raise RuntimeError('fit_report is not available in a frame-sharded run (world > 1): report on the gathered '
+                               'result of get_optimized_variables() in one process')
+        e = self.engine
+        T, N = self.num_frames, self.num_people
+        H, W = self.img_h, self.img_w
+        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
+        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
+            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
+        idx = idx.astype(np.int64)
+        chunk = max(1, int(chunk))
+        scene = getattr(self, '_report_scene', None)
+        if scene is None and self.scene_depth is not None and getattr(self, 'scene_mask', None) is not None:
+            scene = (self.scene_depth, self.scene_mask)
+        cloud = None if scene is None or self.scene_pcd is None else self.scene_pcd.view(-1, 3)
+        staged = bool(getattr(self, '_staged', False))
+        imgs = staged and e.has_images
+        g = self.get_optimized_variables()
+        min_z, max_z = g['min_z'].reshape(T).astype(np.float32), g['max_z'].reshape(T).astype(np.float32)
+        pose2d = e.pose2d.view(T, N, 17, 3) if staged else torch.as_tensor(self._pose2d_init).to(self.device)
+        m = self.SMPLPY.body_model
+        parts = []
+        with torch.cuda.device(self.device), torch.no_grad():
+            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
+            for f0 in range(0, len(idx), chunk):
+                fr = idx[f0:f0 + chunk]
+                need = np.unique(np.concatenate([fr, fr[fr > 0] - 1]))        # the frames and their predecessors, each once
+                sel = torch.as_tensor(need, device=self.device)
+                nb = len(need) * N
+                vall, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[sel].reshape(nb, 72), e.leaf('xscale').view(N),
+                                              pT_all[sel].reshape(nb, 3), want_vposed=False)
+                vall = vall.view(len(need), N, -1, 3)
+                at = torch.as_tensor(np.searchsorted(need, fr), device=self.device)
+                before = torch.as_tensor(np.searchsorted(need, np.maximum(fr - 1, 0)), device=self.device)
+                verts, prev = vall[at].contiguous(), vall[before].contiguous()
+                cur = torch.as_tensor(fr, device=self.device)
+                joints = m.joints_regress(self._joints_reg[0], verts.view(len(fr) * N, -1, 3), corr=pT_all[cur].reshape(len(fr) * N, 3),
+                                          root=self._joints_reg[1])
+                got = report.fit_report(
+                    m, verts, self.cam_K, (W, H), bits=e.bits[cur] if imgs else None, disp=e.depths[cur] if imgs else None,
+                    min_z=min_z[fr] if imgs else None, max_z=max_z[fr] if imgs else None,
+                    scene_depth=None if scene is None else np.asarray(scene[0], np.float32),
+                    scene_mask=None if scene is None else np.asarray(scene[1]) != 0, scene_points=cloud,
+                    joints=joints.view(len(fr), N, 17, 3), pose2d=pose2d[cur], cam_dist_coef=self.cam_dist_coef,
+                    joint_confidence_thr=self.joint_confidence_thr, verts_prev=prev, has_prev=fr > 0, margin=margin, chunk=chunk)
+                parts.append({k: v.cpu().numpy() for k, v in got.items()})
+                del vall, verts, prev, got
+        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+        out['valid'] = self._valid.reshape(T, N)[idx].copy()
         out['frames'] = idx
         return out
 
