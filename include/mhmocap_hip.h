@@ -728,6 +728,61 @@ int mh_fit_report_verts(int B, int V, int H, int W, const float* K /*HOST 3x3*/,
                         const uint8_t* scene_mask /*(H,W)*/, float margin,
                         int32_t* pen_count /*(B)*/, float* pen_max /*(B)*/, void* stream);
 
+/* ---- free-viewpoint render of the fit: meshes and scene point cloud, any camera ---------------------
+ * The third member of the result family (mh_scene_composite: the input view as images,
+ * mh_fit_report_*: the input view in numbers): the side or top view, where depth, scale and contact
+ * errors show.  Replaces the reference's interactive Open3D window (mhmocap/visualization.py) on a
+ * headless device.  A hard z-buffer of its own, ALL INTEGER after the projection (csrc/mh_view.hip
+ * states the conventions in full); nothing of the fit's rasteriser is used.  Every call checks its
+ * arguments before any HIP call, owns nothing and keeps nothing.
+ *
+ * Fixed point: screen in 1/64 pixel, xq = rint(u 64), yq = rint(v 64), u = fx xc / zc + cx,
+ * v = fy yc / zc + cy, (xc,yc,zc) = R X + t in float32 (x right, y down, z forward); pixel (px,py) has
+ * its centre at (64 px + 32, 64 py + 32).  Depth zq = rint(zc 4096), valid 1 <= zq < 2^20 (< 256 m).
+ * An entry is INVALID -- written as (INT32_MIN, 0, 0) -- if zc < near (or NaN), zq is out of range or
+ * |xq| or |yq| >= 2^18 (a guard band of +-4096 px).  H, W <= 4096.
+ *
+ * mh_view_project: count entries xyz -> out_q (xq, yq, zq) int32 under Tv <= 64 views R (Tv,3,3),
+ *   t (Tv,3), K 3x3, all three HOST; near > 0.  per_view = 1: xyz holds Tv consecutive blocks of count
+ *   entries, block i is projected with view i (bodies of Tv frames); per_view = 0: the same count
+ *   entries under each view, out_q is (Tv,count,3) (the scene cloud).
+ * mh_view_clear: keys (T,H,W) = empty (all ones).
+ * mh_view_raster: draws the F faces of T N bodies, vq (T*N,V,3) from mh_view_project, into keys the
+ *   caller has initialised.  A face with an invalid vertex is dropped; FACES ARE NOT CLIPPED.  Both
+ *   windings are drawn, zero area is skipped.  E0, E1, E2 = integer edge functions at the pixel centre
+ *   signed so that their sum A is positive: covered iff all three >= 0 (inclusive edges), depth
+ *   zpix = (E0 z0 + E1 z1 + E2 z2) // A in int64 (< 2^61).  key = zpix << 32 | (n F + f), combined by
+ *   ONE 64-bit unsigned atomic minimum per covered pixel: exact in any order, the same bits on every
+ *   launch.  One lane per face walks a clipped box of up to 16 pixels; a larger box is drawn by the
+ *   whole wave.  N <= 32, N F < 2^31.
+ * mh_view_splat: draws P points pq (T,P,3) into the same keys: the square of 2 half + 1 pixels around
+ *   the pixel (xq >> 6, yq >> 6), clipped to the image, at depth zq, half = min(max_half,
+ *   (size_q fq // zq) // 128), size_q (P) = rint(extent in metres x 4096) (NULL or negative: 0),
+ *   fq = rint(fx 64) > 0, 0 <= max_half <= 8.  key = zq << 32 | 0x80000000 | point: at an exact depth
+ *   tie a mesh beats the scene, a lower person a higher one, a lower point a higher one.
+ * mh_view_resolve: keys as the calls above left them -> images.  depth = zpix / 4096 (-1 = empty);
+ *   label = person, -2 = scene, -1 = empty; face = face of the person / point of the scene / -1;
+ *   image: 255 palette[person] shade for a person -- shade = ambient + (1 - ambient) max(0, -n.light),
+ *   n the geometric normal of the face from verts_view (T*N,V,3, the vertices in VIEW space) flipped
+ *   so that n_z <= 0: formula and rounding of mh_scene_composite -- point_rgb[point] (NULL: mid-grey)
+ *   for the scene, background where empty; coverage[t] = pixels of person 0..N-1, then of the scene
+ *   (integer sums, zeroed by the call).  palette (N,3) DEVICE; light, background HOST.  Each output
+ *   may be NULL (the image's inputs may then be NULL too); all NULL is an error.                    */
+int mh_view_project(int count, int per_view, int Tv, const float* xyz,
+                    const float* R_host /*(Tv,3,3)*/, const float* t_host /*(Tv,3)*/,
+                    const float* K_host /*3x3*/, float near, int32_t* out_q, void* stream);
+int mh_view_clear(int T, int H, int W, uint64_t* keys /*(T,H,W)*/, void* stream);
+int mh_view_raster(int T, int N, int V, int F, int H, int W, const int32_t* vq /*(T*N,V,3)*/,
+                   const int32_t* faces /*(F,3)*/, uint64_t* keys, void* stream);
+int mh_view_splat(int T, int P, int H, int W, const int32_t* pq /*(T,P,3)*/,
+                  const int32_t* size_q /*(P)*/, int fq, int max_half, uint64_t* keys, void* stream);
+int mh_view_resolve(int T, int N, int V, int F, int H, int W, const uint64_t* keys,
+                    const float* verts_view, const int32_t* faces, const uint8_t* point_rgb /*(P,3)*/,
+                    const float* palette /*(N,3) DEVICE*/, const float* light_host /*3*/, float ambient,
+                    const uint8_t* background_host /*3*/, uint8_t* image /*(T,H,W,3)*/,
+                    float* depth /*(T,H,W)*/, int32_t* label, int32_t* face,
+                    int32_t* coverage /*(T,N+1)*/, void* stream);
+
 /* ---- stand-alone forms of losses.py:19-40 and morphology.py:6-41 (call compatibility of
  * mhmocap.losses / mhmocap.morphology; the optimiser uses the fused kernels above) --------------
  * mh_avg_depth_loss: rows = b*N maps of P pixels; `tru` has rows/group maps (group = N when the

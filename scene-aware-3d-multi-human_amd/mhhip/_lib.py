@@ -184,6 +184,11 @@ def lib():
         L.mh_scene_composite.argtypes = [ctypes.c_int] * 6 + [vp] * 5 + [c_float_p, ctypes.c_float, ctypes.c_float] + [vp] * 8
         L.mh_fit_report_pixels.argtypes = [ctypes.c_int] * 4 + [vp] * 8 + [ctypes.c_float] * 2 + [vp] * 3
         L.mh_fit_report_verts.argtypes = [ctypes.c_int] * 4 + [c_float_p] + [vp] * 3 + [ctypes.c_float] + [vp] * 3
+        L.mh_view_project.argtypes = [ctypes.c_int] * 3 + [vp, c_float_p, c_float_p, c_float_p, ctypes.c_float, vp, vp]
+        L.mh_view_clear.argtypes = [ctypes.c_int] * 3 + [vp, vp]
+        L.mh_view_raster.argtypes = [ctypes.c_int] * 6 + [vp] * 4
+        L.mh_view_splat.argtypes = [ctypes.c_int] * 4 + [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
+        L.mh_view_resolve.argtypes = [ctypes.c_int] * 6 + [vp] * 5 + [c_float_p, ctypes.c_float, ctypes.POINTER(ctypes.c_uint8)] + [vp] * 6
         L.mh_avg_depth_loss.argtypes =[vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, vp, vp, vp]
         L.mh_avg_depth_loss_backward.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, vp, ctypes.c_float, vp, vp, vp]
         L.mh_masked_mse.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, vp]

@@ -697,6 +697,66 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         out['frames'] = idx
         return out
 
+    # -- the fit from the side or from above (the reference opens an Open3D window, visualization.py) ---------------------
+    def render_view(self, view, frames=None, image_size=None, K=None, scene=True, splat=1.0, **kw):
+        """Render the current leaves at ``frames`` (default: all) from ANOTHER camera: ``view`` = (R (3,3), t (3)) or
+        ((len(frames),3,3), (len(frames),3)) with x_view = R x + t in the fit camera's space (``mhhip.view.look_at``, ``orbit``,
+        ``top_down``), ``image_size`` (W,H) and ``K`` of the view (default: the fit's).  The vertices of ``predict`` are drawn
+        by ``mhhip.view.render_view`` into one z-buffer with the scene (``scene=True`` and there is one: the depth map and
+        mask ``fit_report`` uses -- the last ``update_scene_pointcloud`` / scene update, else ``scene_depth`` with
+        ``scene_mask``): its masked pixels unprojected under the fit camera (pixel centres at +0.5), coloured by ``scene_img``
+        (mid-grey without one), every point ``splat`` * depth / fx metres wide, so that a depth pixel keeps its metric
+        footprint.  Returns numpy arrays -- image, depth, label (person, -2 = scene, -1 = empty), face, coverage (people,
+        then the scene) -- plus ``'frames'``.  ``kw`` goes to ``mhhip.view.render_view`` (palette, light, ambient, background,
+        near, max_half, outputs, chunk).  Reads the leaves only: buffers of its own, nothing of the engine's state is written."""
+        from mhhip import view as mhview
+        if self.engine is None:
+            raise RuntimeError('render_view: nothing to render before init_optimized_variables()')
+        if self._world()[0] > 1:
+            raise RuntimeError('render_view is not available in a frame-sharded run (world > 1): render from the gathered '
+                               'result of get_optimized_variables() in one process')
+        e = self.engine
+        T, N = self.num_frames, self.num_people
+        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
+        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
+            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
+        idx = idx.astype(np.int64)
+        size = (self.img_w, self.img_h) if image_size is None else (int(image_size[0]), int(image_size[1]))
+        K = self.cam_K if K is None else K
+        R, t = mhview._views(view, len(idx))
+        cloud = rgb = extent = None
+        found = getattr(self, '_report_scene', None)
+        if found is None and self.scene_depth is not None and getattr(self, 'scene_mask', None) is not None:
+            found = (self.scene_depth, self.scene_mask)
+        if scene and found is not None:
+            img = getattr(self, 'scene_img', None)
+            if img is not None:
+                img = np.asarray(img)
+                img = (img if img.dtype == np.uint8 else np.clip(np.rint(img), 0, 255).astype(np.uint8)).reshape(self.img_h, self.img_w, 3)
+            cloud, rgb, extent, _ = mhview.cloud_from_depth(np.asarray(found[0], np.float32).reshape(self.img_h, self.img_w),
+                                                            np.asarray(found[1]).reshape(self.img_h, self.img_w), self.cam_K, img, splat)
+            if len(cloud) == 0:
+                cloud = rgb = extent = None
+        chunk = max(1, int(kw.pop('chunk', 32)))
+        sel = torch.as_tensor(idx, device=self.device)
+        with torch.cuda.device(self.device), torch.no_grad():
+            pT = e.leaf('poses_T').view(T, N, 3)[sel]
+            pose = e.leaf('poses_smpl').view(T, N, 72)[sel]
+            if cloud is not None:
+                cloud, rgb, extent = (torch.as_tensor(a).to(self.device) for a in (cloud, rgb, extent))
+            parts = []
+            for f0 in range(0, len(idx), chunk):
+                sl = slice(f0, min(len(idx), f0 + chunk))
+                nb = (sl.stop - sl.start) * N
+                verts, _, _, _ = self.SMPLPY.body_model.lbs_forward(e.leaf('betas').view(N, 10), pose[sl].reshape(nb, 72),
+                                                                    e.leaf('xscale').view(N), pT[sl].reshape(nb, 3), want_vposed=False)
+                got = mhview.render_view(self.SMPLPY.body_model, verts.view(sl.stop - sl.start, N, -1, 3), (R[sl], t[sl]), K, size,
+                                         cloud=cloud, cloud_rgb=rgb, cloud_size_m=extent, chunk=chunk, **kw)
+                parts.append({k: v.cpu().numpy() for k, v in got.items()})
+        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+        out['frames'] = idx
+        return out
+
     # -- the fit in numbers (the reference has scatter plots to look at, predict.py:141-257) -----------------------------
     def fit_report(self, frames=None, margin=0.05, chunk=32):
         """Per frame and per person, how well the current leaves fit at ``frames`` (default: all): dict of numpy arrays of
