@@ -728,6 +728,61 @@ int mh_fit_report_verts(int B, int V, int H, int W, const float* K /*HOST 3x3*/,
                         const uint8_t* scene_mask /*(H,W)*/, float margin,
                         int32_t* pen_count /*(B)*/, float* pen_max /*(B)*/, void* stream);
 
+/* ---- scene penetration as a term of the fit: the backward half of mh_fit_report_verts ---------------
+ * The reference has no such term (its only scene term, contact, looks at one vertex per body); it is
+ * opt-in.  Every vertex is compared with the scene's depth map, BILINEARLY interpolated: on a planar
+ * piece n . X = d of the scene the gradient of p (below) is s n + ((p + margin) / z) e_z with
+ * s = D / (z n . ray) -- parallel to the plane's normal for a vertex ON the surface, tilted towards the
+ * optical axis by (p + margin) / z <= (band + margin) / z for one behind it (a nearest-pixel lookup
+ * has no slopes and could only push a body towards the camera).
+ *
+ * mh_scene_zmap: zmap[i] = mask[i] > 0.5 ? depth[i] : 0 -- the scene z-map (H,W): the post-processed
+ *   scene depth where the scene mask (float32, as mh_scene_postprocess / mh_scene_points read it) is
+ *   set, 0 where there is no scene.
+ *
+ * mh_scene_pen_term: verts (B,V,3) camera space, K HOST 3x3, zmap (H,W), margin >= 0, band > 0,
+ *   edge > 0.  For a vertex (x,y,z) with z > 0:
+ *     u = fx x / z + cx, v = fy y / z + cy (pixel centres at +0.5, as mh_scene_unproject and
+ *     mh_fit_report_verts), i0 = floor(u - 0.5), j0 = floor(v - 0.5), a = u - 0.5 - i0,
+ *     b = v - 0.5 - j0; taps D00 = zmap[j0][i0], D10 = zmap[j0][i0+1], D01 = zmap[j0+1][i0],
+ *     D11 = zmap[j0+1][i0+1].
+ *   The vertex is SKIPPED (contributes nothing) unless all four taps lie inside the image, all four
+ *   are > 0 and max - min of the four is <= edge (a depth discontinuity: the bilinear slope there is
+ *   meaningless and huge).  Otherwise
+ *     D  = (1-b)((1-a) D00 + a D10) + b((1-a) D01 + a D11),
+ *     Du = (1-b)(D10 - D00) + b(D11 - D01),   Dv = (1-a)(D01 - D00) + a(D11 - D10),
+ *     p  = z - D - margin,   ACTIVE iff 0 < p < band
+ *   (monocular scene depth is the front surface: a body far behind it is occluded, not inside).
+ *   Value: L_b = (1/V) sum_active p^2 per body; the term is coef sum_b L_b.
+ *   Out: body_loss[b] = coef L_b (may be NULL); gverts (B,V,3) (may be NULL) is ADDED to, for an active
+ *   vertex with g = 2 coef p / V:
+ *     d/dx = -g Du fx / z,   d/dy = -g Dv fy / z,   d/dz = g (1 + (Du fx x + Dv fy y) / z^2).
+ *   One lane per vertex; every vertex is owned by one lane, so the add is a plain load, add and store
+ *   (no float atomics; the caller orders the launch behind whatever else writes gverts, as with the
+ *   contact term).  Everything is float32, evaluated in the order written above without fused
+ *   multiply-adds.  The per-body sum of p^2 is a 64-BIT FIXED-POINT INTEGER of 2^-40 m^2 -- integer
+ *   atomics in LDS, one integer atomic per workgroup and body in device memory, exact in any order --
+ *   rounded to float32 once: the same bits on every launch (band^2 V < 2^23 m^2 is checked).
+ *   V need not be a multiple of the workgroup (256) and a workgroup may straddle bodies.
+ *   acc: accumulators owned by the caller, 8 bytes per body (8 * B bytes; cleared by the call), or NULL: obtained from
+ *   and returned to the stream's memory pool inside the call, as mh_fit_report_pixels does -- not on
+ *   a stream that is being captured, where NULL is an error.  Unused when body_loss is NULL.
+ *
+ * mh_scene_pen_term_sel: the gated form for a captured cycle, behind the same device-resident words
+ *   as mh_contact_knn_grid_sel: words[0] = 0 -- no scene yet: gverts is not touched and body_loss is
+ *   0; otherwise the map is zmap0 (words[1] = 0) or zmap1.                                          */
+int mh_scene_zmap(int H, int W, const float* depth /*(H,W)*/, const float* mask /*(H,W) f32*/,
+                  float* zmap /*(H,W)*/, void* stream);
+int mh_scene_pen_term(int B, int V, int H, int W, const float* K_host /*3x3*/,
+                      const float* verts /*(B,V,3)*/, const float* zmap /*(H,W)*/, float coef,
+                      float margin, float band, float edge, float* gverts /*(B,V,3)*/,
+                      float* body_loss /*(B)*/, void* acc /*8 * B bytes or NULL*/, void* stream);
+int mh_scene_pen_term_sel(int B, int V, int H, int W, const float* K_host /*3x3*/,
+                          const float* verts /*(B,V,3)*/, const float* zmap0, const float* zmap1,
+                          const int32_t* words /*[scene live, which map]*/, float coef, float margin,
+                          float band, float edge, float* gverts /*(B,V,3)*/, float* body_loss /*(B)*/,
+                          void* acc /*8 * B bytes or NULL*/, void* stream);
+
 /* ---- free-viewpoint render of the fit: meshes and scene point cloud, any camera ---------------------
  * The third member of the result family (mh_scene_composite: the input view as images,
  * mh_fit_report_*: the input view in numbers): the side or top view, where depth, scale and contact

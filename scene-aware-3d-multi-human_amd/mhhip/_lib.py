@@ -184,6 +184,9 @@ def lib():
         L.mh_scene_composite.argtypes = [ctypes.c_int] * 6 + [vp] * 5 + [c_float_p, ctypes.c_float, ctypes.c_float] + [vp] * 8
         L.mh_fit_report_pixels.argtypes = [ctypes.c_int] * 4 + [vp] * 8 + [ctypes.c_float] * 2 + [vp] * 3
         L.mh_fit_report_verts.argtypes = [ctypes.c_int] * 4 + [c_float_p] + [vp] * 3 + [ctypes.c_float] + [vp] * 3
+        L.mh_scene_zmap.argtypes = [ctypes.c_int] * 2 + [vp] * 4
+        L.mh_scene_pen_term.argtypes = [ctypes.c_int] * 4 + [c_float_p] + [vp] * 2 + [ctypes.c_float] * 4 + [vp] * 4
+        L.mh_scene_pen_term_sel.argtypes = [ctypes.c_int] * 4 + [c_float_p] + [vp] * 4 + [ctypes.c_float] * 4 + [vp] * 4
         L.mh_view_project.argtypes = [ctypes.c_int] * 3 + [vp, c_float_p, c_float_p, c_float_p, ctypes.c_float, vp, vp]
         L.mh_view_clear.argtypes = [ctypes.c_int] * 3 + [vp, vp]
         L.mh_view_raster.argtypes = [ctypes.c_int] * 6 + [vp] * 4

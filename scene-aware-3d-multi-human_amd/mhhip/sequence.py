@@ -23,6 +23,9 @@ LOG_KEYS = ['loss_pose24j', 'loss_depth', 'loss_silhouette', 'reg_ref_poses', 'r
             'reg_foot_sliding', 'reg_vel', 'reg_filter_verts']
 COEF_KEYS = ['proj2d', 'depth', 'silhouette', 'reg_velocity', 'reg_verts_filter', 'reg_poses', 'reg_scales',
              'reg_contact', 'reg_foot_sliding']
+# the opt-in scene-penetration term (mh_scene_pen_term; the reference has none): coefficient and the three lengths in metres
+PEN_DEFAULTS = dict(reg_scene_pen=0.0, scene_pen_margin=0.05, scene_pen_band=0.5, scene_pen_edge=0.25)
+PEN_LOG = 12                             # its slot of the 16-wide log row
 
 
 # The two extra streams of an engine (side branch of the cycle, scene update) are shared by all engines of a device:
@@ -71,8 +74,13 @@ class SequenceEngine(object):
         self.K = np.ascontiguousarray(np.asarray(cam_K, np.float32).reshape(3, 3))
         self.Kd = None if cam_dist_coef is None else np.ascontiguousarray(np.asarray(cam_dist_coef, np.float32))
         c = {k: 1.0 for k in COEF_KEYS}
+        c.update(PEN_DEFAULTS)
         c.update(coefs or {})
         self.c = c
+        self._pen = float(c['reg_scene_pen']) != 0.0
+        if self._pen and not (float(c['scene_pen_margin']) >= 0 and float(c['scene_pen_band']) > 0 and float(c['scene_pen_edge']) > 0):
+            raise ValueError('scene penetration term: scene_pen_margin >= 0, scene_pen_band > 0 and scene_pen_edge > 0, got %r, %r, %r'
+                             % (c['scene_pen_margin'], c['scene_pen_band'], c['scene_pen_edge']))
         self.thr, self.eps = float(joint_confidence_thr), float(eps)
         T, N, B = self.T, self.N, self.B
         self.sizes = [B * 3, B * 72, T, T, N * 10, N]
@@ -111,6 +119,7 @@ class SequenceEngine(object):
         self.scene_pts = None
         self.scene_grid = None
         self.scene_M = 0                 # capacity the grid workspace was sized for
+        self.scene_zmap = None           # z-map of a scene handed in from outside (set_scene_depth): the penetration term's input
         self._scene_dev = None           # device-side scene aggregation state (scene_device_setup)
         self._scene_pending = False
         self.verts_filt = None
@@ -128,6 +137,9 @@ class SequenceEngine(object):
         self._filt_gate = False
         self.batch_frames = None      # batch table of the current cycle (set_batch_table); None = contiguous batches
         self.timing = None            # {name: [(start_event, end_event), ...]} when enabled by bench.py
+        if self._pen:                 # (behind everything else: with the coefficient at 0 no allocation moves)
+            self.pen_body = z(B)
+            self.pen_acc = torch.zeros(B, dtype=torch.int64, device=self.dev)
 
     def enable_timing(self, on=True):
         self.timing = {} if on else None
@@ -254,6 +266,22 @@ class SequenceEngine(object):
         self.scene_pts = None if pts is None else _dev(pts, self.dev).view(-1, 3)
         self._build_scene_grid()
 
+    def set_scene_depth(self, depth, mask):
+        """The scene as maps (H,W) handed in from outside -- post-processed depth and mask, what ``scene_from_depth`` makes
+        its cloud from -- packed into the z-map the penetration term reads (mh_scene_zmap); None: no map.  The term runs
+        behind the contact launches, so it needs the cloud of the same maps as well (``update_scene_pointcloud`` hands over both).
+        The buffer keeps its address from the first call on: captured cycle graphs read it."""
+        if depth is None:
+            self.scene_zmap = None
+            return None
+        H, W = self.H, self.W
+        d = _dev(depth, self.dev).view(H, W)
+        m = _dev(np.asarray(mask, np.float32) if not isinstance(mask, torch.Tensor) else mask.float(), self.dev).view(H, W)
+        if self.scene_zmap is None:
+            self.scene_zmap = torch.zeros(H, W, dtype=torch.float32, device=self.dev)
+        check(_lib.lib().mh_scene_zmap(H, W, ptr(d), ptr(m), ptr(self.scene_zmap), _lib.stream_ptr(self.dev)))
+        return self.scene_zmap
+
     def _build_scene_grid(self):
         self.scene_grid = None
         if self.scene_pts is None or self.scene_pts.shape[0] == 0:
@@ -301,6 +329,9 @@ class SequenceEngine(object):
         d['sets'] = [dict(pts=torch.zeros(P, 3, device=self.dev), count=torch.zeros(1, dtype=torch.int32, device=self.dev),
                           grid=torch.empty(L.mh_scene_grid_bytes(P), dtype=torch.uint8, device=self.dev),
                           zsnap=torch.zeros(2 * T, device=self.dev), ev=torch.cuda.Event()) for _ in range(2)]
+        if self._pen:                 # the maps an update overwrites on another stream are single buffers: one z-map per set
+            for s in d['sets']:
+                s['zmap'] = torch.zeros(H, W, device=self.dev)
         d['next'] = 0                 # set the next update writes
         d['ready'] = None             # set written by the last update, not yet swapped in
         d['front'] = None
@@ -407,6 +438,8 @@ class SequenceEngine(object):
         check(L.mh_scene_points(H, W, self.K.ctypes.data_as(_lib.c_float_p), ptr(d['depth']), ptr(d['ma_mask']), ptr(s['pts']),
                                 ptr(s['count']), st))
         check(L.mh_scene_grid_build_dev(ptr(s['pts']), ptr(s['count']), H * W, ptr(s['grid']), st))
+        if self._pen and 'zmap' in s:        # on the update's stream, in front of the set's event
+            check(L.mh_scene_zmap(H, W, ptr(d['depth']), ptr(d['ma_mask']), ptr(s['zmap']), st))
 
     def scene_device_swap(self):
         """Make the last update the scene the contact term reads from now on (pointer swap; its consumer waits on the
@@ -700,6 +733,8 @@ class SequenceEngine(object):
         scene = self.scene_pts is not None or sel is not None
         filt = self.verts_filt is not None and self.pT_filt is not None
         images = use_images and self.has_images
+        if self._pen and self.halo is not None:
+            raise ValueError('the scene-penetration term (reg_scene_pen != 0) is not available in a frame-sharded run')
         need_gv = scene or filt or (images and raster is not None) or not self.kp_fused
         log = self.tmp_log
         gv = None
@@ -759,8 +794,7 @@ class SequenceEngine(object):
             self._scene_done = False
             sums = [(self.loss2d, log[0:1]), (self.prior_body, log[3:4])]
             if scene and (self._scene_dev is None or scene_ready):     # static scene, or its event already waited for
-                self._scene_terms(s2, reduce=False, sel=sel)
-                sums += [(self.batch_contact, log[5:6]), (self.batch_foot, log[6:7])]
+                sums += self._scene_terms(s2, reduce=False, sel=sel)
                 self._scene_done = True
             _lib.reduce_sum_multi(sums, s2)                            # the small log sums of the side branch: one launch
         # ---- main branch: rasterised depth / silhouette terms ----------------------------------------------------------
@@ -814,7 +848,8 @@ class SequenceEngine(object):
     def _scene_terms(self, st, reduce=True, sel=None):
         """contact + in-batch foot sliding (optimizer.py:485-518) on stream st; gradients by atomics / disjoint writes.
         sel: the two device-built scene sets (``_scene_sel``) -- the launches read the live one through ``phase[1:3]`` and do
-        nothing while there is none."""
+        nothing while there is none.  Behind them the opt-in penetration term (``_scene_pen``).  Returns the (values, slot of the
+        log row) pairs of what was launched; reduce: they are summed here, otherwise by the caller's launch."""
         L = _lib.lib()
         c = self.c
         T, N, B = self.T, self.N, self.B
@@ -832,9 +867,10 @@ class SequenceEngine(object):
                                                 ptr(self.verts), ptr(self.low_idx), ptr(self.low_xyz), ptr(self.dy),
                                                 float(c['reg_contact']), float(c['reg_foot_sliding']), ptr(gpT), ptr(gv),
                                                 ptr(self.batch_contact), ptr(self.batch_foot), words, st))
+            sums = self._scene_sums(self._scene_pen(st, sel))
             if reduce:
-                _lib.reduce_sum_multi([(self.batch_contact, log[5:6]), (self.batch_foot, log[6:7])], st)
-            return
+                _lib.reduce_sum_multi(sums, st)
+            return sums
         if fresh:                                                   # the forward's epilogue has reported the lowest vertices
             check(L.mh_contact_knn_grid_key(ptr(self.scene_grid), self.scene_M, ptr(self.verts), self.V, self._lowkey, B, 32,
                                             ptr(self.low_idx), ptr(self.low_xyz), ptr(self.dy), st))
@@ -850,8 +886,45 @@ class SequenceEngine(object):
             check(L.mh_contact_foot_terms(T, N, self.V, self.batch, ptr(self.verts), ptr(self.low_idx), ptr(self.low_xyz),
                                           ptr(self.dy), float(c['reg_contact']), float(c['reg_foot_sliding']), ptr(gpT),
                                           ptr(gv), ptr(self.batch_contact), ptr(self.batch_foot), st))
+        sums = self._scene_sums(self._scene_pen(st, None))
         if reduce:
-            _lib.reduce_sum_multi([(self.batch_contact, log[5:6]), (self.batch_foot, log[6:7])], st)
+            _lib.reduce_sum_multi(sums, st)
+        return sums
+
+    def _scene_sums(self, pen):
+        """(per-batch or per-body values, their slot of the log row) of the scene terms; pen: the penetration term was launched"""
+        log = self.tmp_log
+        sums = [(self.batch_contact, log[5:6]), (self.batch_foot, log[6:7])]
+        if pen:
+            sums.append((self.pen_body, log[PEN_LOG:PEN_LOG + 1]))
+        return sums
+
+    def _pen_zmap(self):
+        """the z-map of the scene the plain launches read: the live device-built set's, else the one handed in"""
+        d = self._scene_dev
+        if d is not None and d.get('front') is not None and self.scene_pts is d['front']['pts']:
+            return d['front'].get('zmap')
+        return self.scene_zmap
+
+    def _scene_pen(self, st, sel):
+        """the opt-in penetration term (mh_scene_pen_term) on stream st, behind the contact launches: every vertex against the
+        scene's z-map, ADDED into the vertex gradients (each vertex has one owner: no atomics; the stream orders it behind the
+        buffer's initialisation and the foot-sliding adds).  Returns whether it was launched."""
+        if not self._pen:
+            return False
+        L, c = _lib.lib(), self.c
+        Kp = self.K.ctypes.data_as(_lib.c_float_p)
+        tail = (float(c['reg_scene_pen']), float(c['scene_pen_margin']), float(c['scene_pen_band']), float(c['scene_pen_edge']),
+                ptr(self._gv_cur), ptr(self.pen_body), ptr(self.pen_acc), st)
+        if sel is not None:
+            check(L.mh_scene_pen_term_sel(self.B, self.V, self.H, self.W, Kp, ptr(self.verts), ptr(sel[0]['zmap']), ptr(sel[1]['zmap']),
+                                          self.phase.data_ptr() + 4, *tail))
+            return True
+        zmap = self._pen_zmap()
+        if zmap is None:
+            return False
+        check(L.mh_scene_pen_term(self.B, self.V, self.H, self.W, Kp, ptr(self.verts), ptr(zmap), *tail))
+        return True
 
     def _finish_b(self, row, use_images=True, raster=None):
         """scene terms when they could not run in the side branch (eager launches with the cloud rebuilt on the device
@@ -950,8 +1023,14 @@ class SequenceEngine(object):
         L = _lib.lib()
         glob = (L.mh_raster_get_deterministic(), L.mh_raster_get_sort_margin(), L.mh_lbs_get_mode(), L.mh_raster_get_path(),
                 L.mh_raster_get_winners(), float(L.mh_raster_get_sort_defer()), L.mh_lbs_get_forward_pipeline()) if raster is not None else None
+        pen = None
+        if self._pen:                     # the four values are kernel arguments by value; the maps are read by address
+            zm = tuple(x['zmap'].data_ptr() for x in sel) if sel is not None else (None if self._pen_zmap() is None else self._pen_zmap().data_ptr())
+            pen = (float(self.c['reg_scene_pen']), float(self.c['scene_pen_margin']), float(self.c['scene_pen_band']),
+                   float(self.c['scene_pen_edge']), zm)
         hk = None if self.halo is None else (bool(self.halo.get('has_prev')), bool(self.halo.get('has_next')), self.halo.get('poses') is not None)
-        return (rast, scene, self.verts_filt is not None and self.pT_filt is not None, self._filt_gate, hk, bt, glob)
+        key = (rast, scene, self.verts_filt is not None and self.pT_filt is not None, self._filt_gate, hk, bt, glob)
+        return key if pen is None else key + (pen,)
 
     def raster_terms(self, znear=1.0, zfar=100.0):
         """The engine's rasteriser binding (workspace + face table), created once and kept alive with the engine:
@@ -1089,5 +1168,7 @@ class SequenceEngine(object):
             d = {'loss_pose24j': r[0] / nb, 'loss_depth': r[1] / nb, 'loss_silhouette': r[2] / nb,
                  'reg_ref_poses': (r[3] + r[9]) / nb, 'reg_scale': r[10] + r[11], 'reg_contact': r[5] / nb,
                  'reg_foot_sliding': r[6] / nb, 'reg_vel': r[7], 'reg_filter_verts': r[8]}
+            if self._pen:                # a tenth key, only with the term switched on: coef * sum over the bodies of mean p^2
+                d['reg_scene_pen'] = r[PEN_LOG]
             out.append({k: np.float32(v) for k, v in d.items()})
         return out

@@ -46,6 +46,9 @@ class ShardedSequence(object):
         """enabled=False: single-process behaviour even when torch.distributed is initialised (sharding is opt-in)"""
         self.e = engine
         self.group = group
+        if enabled and float((getattr(engine, 'c', None) or {}).get('reg_scene_pen', 0.0)) != 0.0:
+            raise ValueError('the scene-penetration term (reg_scene_pen != 0) is not available in a frame-sharded run: its '
+                             'z-maps follow the single-process scene update')
         on = enabled and dist.is_available() and dist.is_initialized()
         self.rank = dist.get_rank(group) if on else 0
         self.world = dist.get_world_size(group) if on else 1

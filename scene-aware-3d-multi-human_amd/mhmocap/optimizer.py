@@ -100,6 +100,15 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         if shard is None:
             shard = self.process_group is not None or os.environ.get('MHHIP_SHARD_FRAMES') == '1'
         self.shard_frames = bool(shard)
+        # opt-in scene-penetration term (no counterpart in the reference: keywords only, the positional signature stays):
+        # every vertex against the scene's depth map, pushed out along the surface normal (mh_scene_pen_term)
+        self.reg_scene_pen_coef = float(kargs.pop('reg_scene_pen_coef', 0.0))
+        self.scene_pen_margin = float(kargs.pop('scene_pen_margin', 0.05))
+        self.scene_pen_band = float(kargs.pop('scene_pen_band', 0.5))
+        self.scene_pen_edge = float(kargs.pop('scene_pen_edge', 0.25))
+        if self.reg_scene_pen_coef != 0.0 and self.shard_frames:
+            raise ValueError('reg_scene_pen_coef != 0 is not available with frame sharding (shard_frames / process_group / '
+                             'MHHIP_SHARD_FRAMES=1)')
         self._global_cache = None
         super().__init__(**kargs)
         if focal_length is None:
@@ -115,6 +124,9 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
                           reg_velocity=reg_velocity_coef, reg_verts_filter=reg_verts_filter_coef,
                           reg_poses=reg_poses_coef, reg_scales=reg_scales_coef, reg_contact=reg_contact_coef,
                           reg_foot_sliding=reg_foot_sliding_coef)
+        if self.reg_scene_pen_coef != 0.0:          # (at 0 the engine is handed exactly the reference's nine)
+            self.coefs.update(reg_scene_pen=self.reg_scene_pen_coef, scene_pen_margin=self.scene_pen_margin,
+                              scene_pen_band=self.scene_pen_band, scene_pen_edge=self.scene_pen_edge)
         for k in COEF_KEYS:
             setattr(self, {'proj2d': 'proj2d_loss_coef', 'depth': 'depth_loss_coef',
                            'silhouette': 'silhouette_loss_coef'}.get(k, k + '_coef'), self.coefs[k])
@@ -630,6 +642,8 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         self.scene_pcd = pts.unsqueeze(0).unsqueeze(0)                        # (1,1,M,3)
         # the maps the cloud came from, for fit_report (body against scene is measured per pixel of the depth map)
         self._report_scene = (np.array(scene_depth, np.float32), np.asarray(scene_mask, np.float32) > 0.5)
+        if self.reg_scene_pen_coef != 0.0:          # ... and, packed into one z-map, for the penetration term
+            self.engine.set_scene_depth(self._report_scene[0], self._report_scene[1])
 
     # -- reference optimizer.py:619-636 ---------------------------------------------------------------
     def get_optimized_variables(self):
