@@ -783,6 +783,76 @@ int mh_scene_pen_term_sel(int B, int V, int H, int W, const float* K_host /*3x3*
                           float band, float edge, float* gverts /*(B,V,3)*/, float* body_loss /*(B)*/,
                           void* acc /*8 * B bytes or NULL*/, void* stream);
 
+/* ---- depth ordering between the people of a frame: the one term that couples two bodies -------------
+ * The reference has no such term; it is opt-in.  Where the instance masks say "this pixel is person
+ * y and certainly not person n", body y must be in front of body n: the depth-ordering loss of Jiang
+ * et al., "Coherent Reconstruction of Multiple Humans from a Single Image" (CVPR 2020), read off the
+ * nearest-face keys the rasteriser's selection pass leaves for every body SEPARATELY (slot 0 of the
+ * key records, as mh_scene_composite reads them).  One streaming pass over pixels the cycle has
+ * already rasterised.
+ *
+ * Inputs, per frame t and pixel i (row-major in H x W), for body n of the frame (b = t N + n):
+ *   z_n(i) is defined exactly as k_scene_composite decides it: the body's window must lie inside the
+ *     image and its keys inside the key array (T N H W records), the pixel must lie inside the window,
+ *     slot 0 of the pixel's key record must not be all ones and its low word must be < F; z is the
+ *     float in the high word.  A z that is not a finite positive float counts as empty.
+ *   gate (T*N) float, may be NULL = every body takes part.  A body with gate[b] == 0 takes part in
+ *     nothing.
+ *   OWNER: person y < N with bit y of ebits[t][i] set (the twice-eroded words: confidently y), gate
+ *     non-zero and z_y(i) defined.
+ *   OCCLUDER of that owner: person n != y, n < N, with bit n of bits[t][i] CLEAR (the raw words:
+ *     confidently not n), gate non-zero and z_n(i) defined.
+ *   Words are read unsigned, so person 31 is bit 31.
+ * Per (pixel, owner, occluder), all in float32, in exactly this order, with no fused multiply-add:
+ *     d = (z_y - z_n) + margin;  the triple is ACTIVE iff d > 0 (the owner must be in front of everyone
+ *     who is not there according to the masks, by at least margin);
+ *     m = min(d, delta);  r = m * ((d + d) - m)  -- d^2 up to delta and linear beyond it, so the
+ *     gradient 2 m is bounded;  r is clamped to at most 1024.
+ * Sums are 64-BIT FIXED-POINT INTEGERS with q(x) = rint(x 2^24):
+ *     G[y] += q(m), G[n] -= q(m);  R[y] += q(r), C[y] += 1;  if asked for, pairs[t][y][n] += 1.
+ *   Integer atomics accumulate in LDS; one integer atomic per workgroup and accumulator in device
+ *   memory, as mh_fit_report_pixels does it.  The sums are exact in any order: the same bits on every
+ *   launch.  No float atomics anywhere.
+ * Outputs, by a second launch of one lane per body:
+ *     body_loss[b] = cl * float32(double(R[b]) 2^-24),  cl = float32(coef / (H W));
+ *     count[b]     = C[b];
+ *     gtransl[b][2] += cg * float32(double(G[b]) 2^-24), cg = float32(2 coef / (H W)) -- a plain load,
+ *       add and store: the caller orders the launch against other writers of gtransl (T*N,3);
+ *     pairs (T,N,N) int32 is zeroed by the call.
+ *   Each output may be NULL; all NULL is an error.
+ * Consequences: the gradient goes to the z of the root translation ONLY (as the contact term's goes to
+ * its y only); the motion of the barycentrics with the translation, and the scale leaf, are ignored.
+ * Per frame the G of all bodies sum to exactly 0.  With N == 1 nothing is active and gtransl is not
+ * touched.
+ * Argument checks, all before any HIP call: 0 <= margin; 0 < delta <= 1024; N <= 32; N H W <= 2^26 (a
+ * body's sums then stay below 2^26 2^10 2^24 = 2^60 < 2^61 steps); T <= 65535, H <= 4095,
+ * W <= 65535 (the composite's limits); no NULL table.
+ *
+ * mh_order_term_keys takes explicit tables as mh_raster_workspace_offsets describes them: win (T*N,4)
+ *   int32 x0, y0, width, height; koff (T*N) int64 first window pixel of a body in keys; keys (T*N*H*W,5)
+ *   uint64.
+ * mh_order_term resolves the three offsets of a rasteriser workspace `ws` on which a selection pass
+ *   for exactly these T,N,V,F,H,W has run, and calls the first.  Inside the fit's cycle the launch
+ *   sits behind the selection kernel and in front of the rasteriser's gradient half: nothing runs in
+ *   between on that stream, and the gradient half itself (k_raster_grads, k_raster_grads_det, the
+ *   deferred face sorts that ride in it) only READS the windows and the keys -- the windows are written
+ *   by k_raster_prepare and the keys by k_raster_strip alone.
+ * acc: accumulators owned by the caller, 24 bytes per body (24 * T * N bytes; cleared by the call), or
+ *   NULL: obtained from and returned to the stream's memory pool inside the call, as
+ *   mh_scene_pen_term does -- not on a stream that is being captured, where NULL is an error.
+ * Both calls own nothing and keep nothing.                                                            */
+int mh_order_term_keys(int T, int N, int F, int H, int W, const int32_t* win /*(T*N,4)*/,
+                       const int64_t* koff /*(T*N)*/, const uint64_t* keys /*(T*N*H*W,5)*/,
+                       const uint32_t* bits /*(T,H,W)*/, const uint32_t* ebits /*(T,H,W)*/,
+                       const float* gate /*(T*N) or NULL*/, float coef, float margin, float delta,
+                       float* gtransl /*(T*N,3)*/, float* body_loss /*(T*N)*/, int32_t* count /*(T*N)*/,
+                       int32_t* pairs /*(T,N,N)*/, void* acc /*24 * T * N bytes or NULL*/, void* stream);
+int mh_order_term(int T, int N, int V, int F, int H, int W, const void* ws,
+                  const uint32_t* bits /*(T,H,W)*/, const uint32_t* ebits /*(T,H,W)*/,
+                  const float* gate /*(T*N) or NULL*/, float coef, float margin, float delta,
+                  float* gtransl /*(T*N,3)*/, float* body_loss /*(T*N)*/, int32_t* count /*(T*N)*/,
+                  int32_t* pairs /*(T,N,N)*/, void* acc /*24 * T * N bytes or NULL*/, void* stream);
+
 /* ---- free-viewpoint render of the fit: meshes and scene point cloud, any camera ---------------------
  * The third member of the result family (mh_scene_composite: the input view as images,
  * mh_fit_report_*: the input view in numbers): the side or top view, where depth, scale and contact

@@ -160,6 +160,30 @@ def render(model, verts, cam_K, image_size):
     return zbuf, alpha
 
 
+def selection_zeros(dims, dev):
+    """the inputs of the rasterised terms, all zero (the validity gate and the silhouette denominator one), for ``selection_pass``
+    on up to dims[0] frames"""
+    T, N, _, _, H, W = dims
+    zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+    zf = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+    return dict(bits=zi(T, H, W), depths=zf(T, H, W), tz=zf(T), zb=zf(T * N), ones=torch.ones(T * N, device=dev), front=zi(T * N),
+                dbody=zf(T * N), sbody=zf(T * N))
+
+
+def selection_pass(dims, K, verts, faces, ws, st, zeros=None):
+    """The selection pass alone (phases = 1 of ``mh_raster_terms_phase``, loss coefficients 0, no gradients, no images) for
+    dims = (T,N,V,F,H,W) on workspace ``ws``: only the windows and keys it leaves there are wanted (``mh_scene_composite``,
+    ``mh_order_term``).  The workspace is initialised afresh (its layout follows the frame count: no face list of other frames
+    is kept).  K: host float32 (9); ``zeros``: ``selection_zeros`` for at least dims[0] frames (default: allocated here)."""
+    L = _lib.lib()
+    z = selection_zeros(dims, verts.device) if zeros is None else zeros
+    check(L.mh_raster_workspace_init(*dims, ptr(ws), st))
+    check(L.mh_raster_terms_phase(*dims, K.ctypes.data_as(_lib.c_float_p), ptr(verts), ptr(faces), ptr(z['bits']), ptr(z['bits']),
+                                  ptr(z['depths']), ptr(z['tz']), ptr(z['tz']), ptr(z['ones']), ptr(z['front']), ptr(z['zb']),
+                                  ptr(z['ones']), ptr(z['zb']), 0.0, 0.0, 1e-3, None, None, None, ptr(z['dbody']), ptr(z['sbody']),
+                                  ptr(ws), None, None, 1, st))
+
+
 SCENE_OUTPUTS = ('depth', 'person', 'face', 'normal', 'overlay', 'visible', 'coverage')
 
 
@@ -217,22 +241,14 @@ def render_scene(model, verts, cam_K, image_size, images=None, palette=None, lig
                       normal=((T, H, W, 3), torch.float32), overlay=((T, H, W, 3), torch.uint8), visible=((T, N, V), torch.uint8),
                       coverage=((T, N), torch.int32))
         out = {k: (torch.zeros if k == 'visible' else torch.empty)(shapes[k][0], dtype=shapes[k][1], device=dev) for k in names}
-        # the inputs of the rasterised terms, all zero: only the windows and keys of the selection pass are wanted
-        zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
-        zf = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-        bits, depths, tz, zb, ones = zi(chunk, H, W), zf(chunk, H, W), zf(chunk), zf(chunk * N), torch.ones(chunk * N, device=dev)
-        front, dbody, sbody = zi(chunk * N), zf(chunk * N), zf(chunk * N)
+        zeros = selection_zeros((chunk, N, V, F, H, W), dev)
         K = np.ascontiguousarray(np.asarray(cam_K, np.float32).reshape(9))
         ws = torch.empty(L.mh_raster_workspace_bytes(chunk, N, V, F, H, W), dtype=torch.uint8, device=dev)
         for t0 in range(0, T, chunk):
             tc = min(chunk, T - t0)
             dims = (tc, N, V, F, H, W)
             v = verts[t0:t0 + tc]
-            # a fresh workspace for every chunk (its layout follows the frame count): no face list of other frames is kept
-            check(L.mh_raster_workspace_init(*dims, ptr(ws), st))
-            check(L.mh_raster_terms_phase(*dims, K.ctypes.data_as(_lib.c_float_p), ptr(v), ptr(faces), ptr(bits), ptr(bits),
-                                          ptr(depths), ptr(tz), ptr(tz), ptr(ones), ptr(front), ptr(zb), ptr(ones), ptr(zb),
-                                          0.0, 0.0, 1e-3, None, None, None, ptr(dbody), ptr(sbody), ptr(ws), None, None, 1, st))
+            selection_pass(dims, K, v, faces, ws, st, zeros)
             o = lambda k: ptr(out[k][t0:t0 + tc]) if k in out else None
             check(L.mh_scene_composite(*dims, ptr(v), ptr(faces), ptr(ws), None if images is None else ptr(images[t0:t0 + tc]),
                                        ptr(pal), lgt.ctypes.data_as(_lib.c_float_p), float(ambient), float(alpha), o('depth'),

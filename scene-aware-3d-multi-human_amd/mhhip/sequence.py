@@ -26,6 +26,10 @@ COEF_KEYS = ['proj2d', 'depth', 'silhouette', 'reg_velocity', 'reg_verts_filter'
 # the opt-in scene-penetration term (mh_scene_pen_term; the reference has none): coefficient and the three lengths in metres
 PEN_DEFAULTS = dict(reg_scene_pen=0.0, scene_pen_margin=0.05, scene_pen_band=0.5, scene_pen_edge=0.25)
 PEN_LOG = 12                             # its slot of the 16-wide log row
+# the opt-in depth-ordering term between the people of a frame (mh_order_term; the reference has none): coefficient, margin and
+# the depth difference from which the penalty grows linearly, in metres
+ORDER_DEFAULTS = dict(reg_order=0.0, order_margin=0.05, order_delta=0.5)
+ORDER_LOG = 13                           # its slot of the 16-wide log row
 
 
 # The two extra streams of an engine (side branch of the cycle, scene update) are shared by all engines of a device:
@@ -75,12 +79,17 @@ class SequenceEngine(object):
         self.Kd = None if cam_dist_coef is None else np.ascontiguousarray(np.asarray(cam_dist_coef, np.float32))
         c = {k: 1.0 for k in COEF_KEYS}
         c.update(PEN_DEFAULTS)
+        c.update(ORDER_DEFAULTS)
         c.update(coefs or {})
         self.c = c
         self._pen = float(c['reg_scene_pen']) != 0.0
         if self._pen and not (float(c['scene_pen_margin']) >= 0 and float(c['scene_pen_band']) > 0 and float(c['scene_pen_edge']) > 0):
             raise ValueError('scene penetration term: scene_pen_margin >= 0, scene_pen_band > 0 and scene_pen_edge > 0, got %r, %r, %r'
                              % (c['scene_pen_margin'], c['scene_pen_band'], c['scene_pen_edge']))
+        self._order = float(c['reg_order']) != 0.0
+        if self._order and not (float(c['order_margin']) >= 0 and 0 < float(c['order_delta']) <= 1024):
+            raise ValueError('depth-ordering term: order_margin >= 0 and 0 < order_delta <= 1024, got %r, %r'
+                             % (c['order_margin'], c['order_delta']))
         self.thr, self.eps = float(joint_confidence_thr), float(eps)
         T, N, B = self.T, self.N, self.B
         self.sizes = [B * 3, B * 72, T, T, N * 10, N]
@@ -140,6 +149,10 @@ class SequenceEngine(object):
         if self._pen:                 # (behind everything else: with the coefficient at 0 no allocation moves)
             self.pen_body = z(B)
             self.pen_acc = torch.zeros(B, dtype=torch.int64, device=self.dev)
+        if self._order:               # (likewise; the accumulators are the caller's because the launch is captured)
+            self.order_body = z(B)
+            self.order_acc = torch.zeros(B, 3, dtype=torch.int64, device=self.dev)
+            self.order_gate = None    # p2d_valid * mask_valid, built once at staging
 
     def enable_timing(self, on=True):
         self.timing = {} if on else None
@@ -255,6 +268,8 @@ class SequenceEngine(object):
             self.has_images = True
         check(L.mh_stage_gates(ptr(self.pose2d), ptr(self.area), self.B, self.thr, 0.005 * H * W, ptr(self.p2d_valid),
                                ptr(self.mask_valid), st))
+        if self._order:
+            self.order_gate = (self.p2d_valid * self.mask_valid).contiguous()
         self.low_idx = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
         self.low_xyz = torch.zeros(self.B, 3, dtype=torch.float32, device=self.dev)
         self.dy = torch.zeros(self.B, dtype=torch.float32, device=self.dev)
@@ -735,6 +750,8 @@ class SequenceEngine(object):
         images = use_images and self.has_images
         if self._pen and self.halo is not None:
             raise ValueError('the scene-penetration term (reg_scene_pen != 0) is not available in a frame-sharded run')
+        if self._order and self.halo is not None:
+            raise ValueError('the depth-ordering term (reg_order != 0) is not available in a frame-sharded run')
         need_gv = scene or filt or (images and raster is not None) or not self.kp_fused
         log = self.tmp_log
         gv = None
@@ -833,6 +850,7 @@ class SequenceEngine(object):
                 # signalled: +0.5 % same-box)
                 main.wait_stream(side)
                 joined = True
+                self._order_term(raster, st)
                 # the closing kernel's job rides in the LBS backward's pose kernel when that is the fused form
                 # (_finish_b): one launch and one dependent kernel less on the chain
                 defer = bool(getattr(self, '_kp_chunk', False)) and os.environ.get('MHHIP_NO_DEFER') != '1'
@@ -925,6 +943,19 @@ class SequenceEngine(object):
             return False
         check(L.mh_scene_pen_term(self.B, self.V, self.H, self.W, Kp, ptr(self.verts), ptr(zmap), *tail))
         return True
+
+    def _order_term(self, raster, st):
+        """the opt-in depth-ordering term (mh_order_term) on the main stream: behind the selection kernel, whose windows and
+        nearest-face keys it reads, and behind the side branch's join (velocity and contact terms add into the same gradient);
+        in front of the rasteriser's gradient half and of the LBS backward, which adds its own part.  The z of the root
+        translation's gradient is a plain load, add and store per body."""
+        if not self._order:
+            return
+        c, log = self.c, self.tmp_log
+        check(_lib.lib().mh_order_term(*raster.dims, ptr(raster.ws), ptr(self.bits), ptr(self.ebits), ptr(self.order_gate),
+                                       float(c['reg_order']), float(c['order_margin']), float(c['order_delta']),
+                                       ptr(self.leaf('poses_T', self.grads)), ptr(self.order_body), None, None, ptr(self.order_acc), st))
+        _lib.reduce_sum_multi([(self.order_body, log[ORDER_LOG:ORDER_LOG + 1])], st)
 
     def _finish_b(self, row, use_images=True, raster=None):
         """scene terms when they could not run in the side branch (eager launches with the cloud rebuilt on the device
@@ -1030,7 +1061,11 @@ class SequenceEngine(object):
                    float(self.c['scene_pen_edge']), zm)
         hk = None if self.halo is None else (bool(self.halo.get('has_prev')), bool(self.halo.get('has_next')), self.halo.get('poses') is not None)
         key = (rast, scene, self.verts_filt is not None and self.pT_filt is not None, self._filt_gate, hk, bt, glob)
-        return key if pen is None else key + (pen,)
+        if pen is not None:
+            key = key + (pen,)
+        if self._order:                   # coefficient, margin and delta are kernel arguments by value
+            key = key + (('order', float(self.c['reg_order']), float(self.c['order_margin']), float(self.c['order_delta'])),)
+        return key
 
     def raster_terms(self, znear=1.0, zfar=100.0):
         """The engine's rasteriser binding (workspace + face table), created once and kept alive with the engine:
@@ -1170,5 +1205,7 @@ class SequenceEngine(object):
                  'reg_foot_sliding': r[6] / nb, 'reg_vel': r[7], 'reg_filter_verts': r[8]}
             if self._pen:                # a tenth key, only with the term switched on: coef * sum over the bodies of mean p^2
                 d['reg_scene_pen'] = r[PEN_LOG]
+            if self._order:              # likewise: coef / (H W) * the sum over the bodies of their ordering residuals
+                d['reg_order'] = r[ORDER_LOG]
             out.append({k: np.float32(v) for k, v in d.items()})
         return out

@@ -49,6 +49,8 @@ class ShardedSequence(object):
         if enabled and float((getattr(engine, 'c', None) or {}).get('reg_scene_pen', 0.0)) != 0.0:
             raise ValueError('the scene-penetration term (reg_scene_pen != 0) is not available in a frame-sharded run: its '
                              'z-maps follow the single-process scene update')
+        if enabled and float((getattr(engine, 'c', None) or {}).get('reg_order', 0.0)) != 0.0:
+            raise ValueError('the depth-ordering term (reg_order != 0) is not available in a frame-sharded run')
         on = enabled and dist.is_available() and dist.is_initialized()
         self.rank = dist.get_rank(group) if on else 0
         self.world = dist.get_world_size(group) if on else 1

@@ -109,6 +109,14 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         if self.reg_scene_pen_coef != 0.0 and self.shard_frames:
             raise ValueError('reg_scene_pen_coef != 0 is not available with frame sharding (shard_frames / process_group / '
                              'MHHIP_SHARD_FRAMES=1)')
+        # opt-in depth-ordering term between the people of a frame (no counterpart in the reference either): where the instance
+        # masks say who occludes whom, the occluded body is pushed behind the other one (mh_order_term)
+        self.reg_order_coef = float(kargs.pop('reg_order_coef', 0.0))
+        self.order_margin = float(kargs.pop('order_margin', 0.05))
+        self.order_delta = float(kargs.pop('order_delta', 0.5))
+        if self.reg_order_coef != 0.0 and self.shard_frames:
+            raise ValueError('reg_order_coef != 0 is not available with frame sharding (shard_frames / process_group / '
+                             'MHHIP_SHARD_FRAMES=1)')
         self._global_cache = None
         super().__init__(**kargs)
         if focal_length is None:
@@ -127,6 +135,8 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         if self.reg_scene_pen_coef != 0.0:          # (at 0 the engine is handed exactly the reference's nine)
             self.coefs.update(reg_scene_pen=self.reg_scene_pen_coef, scene_pen_margin=self.scene_pen_margin,
                               scene_pen_band=self.scene_pen_band, scene_pen_edge=self.scene_pen_edge)
+        if self.reg_order_coef != 0.0:              # (likewise)
+            self.coefs.update(reg_order=self.reg_order_coef, order_margin=self.order_margin, order_delta=self.order_delta)
         for k in COEF_KEYS:
             setattr(self, {'proj2d': 'proj2d_loss_coef', 'depth': 'depth_loss_coef',
                            'silhouette': 'silhouette_loss_coef'}.get(k, k + '_coef'), self.coefs[k])
@@ -836,6 +846,50 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
                 del vall, verts, prev, got
         out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
         out['valid'] = self._valid.reshape(T, N)[idx].copy()
+        out['frames'] = idx
+        return out
+
+    # -- who stands in front of whom, against the instance masks ----------------------------------------------------------
+    def order_report(self, frames=None, margin=None, delta=None, chunk=32):
+        """Per frame and per person, where the current leaves put somebody in front of the person the instance masks show
+        at ``frames`` (default: all): dict of numpy arrays -- the columns of ``mhhip.order.order_terms``, ``order_px``
+        (len(frames), N) violating (pixel, other person) pairs the person owns, ``order_pairs`` (len(frames), N, N) the same by
+        the other person, ``order_loss`` (len(frames), N) the term's value at coefficient 1 -- plus ``'frames'``.  The masks
+        and the gate are the staged ones (a fit, or ``_stage_from_dataloader``, must have run); ``margin`` / ``delta`` default
+        to the optimiser's ``order_margin`` / ``order_delta``.  Reads the leaves only, on a rasteriser workspace of its own."""
+        from mhhip import order
+        if self.engine is None:
+            raise RuntimeError('order_report: nothing to report before init_optimized_variables()')
+        if self._world()[0] > 1:
+            raise RuntimeError('order_report is not available in a frame-sharded run (world > 1): report on the gathered '
+                               'result of get_optimized_variables() in one process')
+        e = self.engine
+        if not (bool(getattr(self, '_staged', False)) and e.has_images):
+            raise RuntimeError('order_report needs the staged instance masks: run fit() (or stage a dataloader with masks) first')
+        T, N = self.num_frames, self.num_people
+        H, W = self.img_h, self.img_w
+        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
+        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
+            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
+        idx = idx.astype(np.int64)
+        chunk = max(1, int(chunk))
+        margin = self.order_margin if margin is None else float(margin)
+        delta = self.order_delta if delta is None else float(delta)
+        m = self.SMPLPY.body_model
+        parts = []
+        with torch.cuda.device(self.device), torch.no_grad():
+            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
+            gate = (e.p2d_valid * e.mask_valid).view(T, N)
+            for f0 in range(0, len(idx), chunk):
+                cur = torch.as_tensor(idx[f0:f0 + chunk], device=self.device)
+                nb = len(cur) * N
+                verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[cur].reshape(nb, 72), e.leaf('xscale').view(N),
+                                               pT_all[cur].reshape(nb, 3), want_vposed=False)
+                got = order.order_terms(m, verts.view(len(cur), N, -1, 3), self.cam_K, (W, H), e.bits[cur], e.ebits[cur],
+                                        gate=gate[cur], margin=margin, delta=delta, chunk=chunk)
+                parts.append({k: v.cpu().numpy() for k, v in got.items()})
+                del verts, got
+        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
         out['frames'] = idx
         return out
 
