@@ -908,6 +908,50 @@ int mh_view_resolve(int T, int N, int V, int F, int H, int W, const uint64_t* ke
                     float* depth /*(T,H,W)*/, int32_t* label, int32_t* face,
                     int32_t* coverage /*(T,N+1)*/, void* stream);
 
+/* ---- body-to-scene contact map: the nearest scene point of every vertex ----------------------------
+ * The fourth member of the result family: which part of a body touches the scene and how far the
+ * rest is from it -- in 3D, against the whole cloud (the contact term and contact_dy_m look at one
+ * vertex per body, the penetration term along camera rays at the front surface).  The reference
+ * answers this through an interactive viewer only.  Read-only, off the cycle; no term of the fit.
+ *
+ * mh_scene_nearest: grid_ws and M exactly as mh_contact_knn_grid takes them (a workspace
+ *   mh_scene_grid_build or mh_scene_grid_build_dev has filled, M = the size it was carved for; the
+ *   number of points is the count the build left on the device, so rows behind a device-side count
+ *   are not part of the cloud); queries (Q,3) on the device; radius in metres.
+ *   For query q and cloud point p, all in float32, in exactly this order, with no fused multiply-add:
+ *       dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;   d2 = (dx dx + dy dy) + dz dz;
+ *       r2 = radius radius;   p is a CANDIDATE iff d2 <= r2.
+ *   d2[q] = the smallest d2 over the candidates; near_xyz[q] = the candidate that attains it, on equal
+ *   d2 the one with the smallest x, then y, then z (coordinates compare as numbers: candidates that
+ *   differ only in the sign of a zero are the same point).  The result is a function of the candidate
+ *   SET and does not depend on the order the cloud is visited in.  Without a candidate, for a query
+ *   with a coordinate that is not finite, and for an empty cloud: d2 = +inf, near_xyz = (0,0,0).
+ *   Either output may be NULL, not both.
+ *   One lane per query, workgroups of 256; a lane walks the rows of cells its box [q - r, q + r] can
+ *   touch -- a superset of every candidate's cell under float32 rounding (csrc/mh_contact.hip argues
+ *   it) -- and a query whose box misses the cloud's bounding box ends after reading the grid's header.
+ *   Refused before any HIP call: Q <= 0, M <= 0, a NULL grid or queries, both outputs NULL, a radius
+ *   that is not finite and positive, and a radius above MH_SCENE_NEAREST_MAX_CELLS cells of the
+ *   smallest cell size a grid can have (0.02 m): 0.64 m.  A box then spans at most
+ *   2 * 32 + 2 = 66 cells per axis, 66^2 rows of cells per query.
+ *
+ * mh_contact_parts: d2 (B,V) as mh_scene_nearest wrote it for B bodies of V vertices; part (V) uint8:
+ *   the part of every vertex, the same for all bodies; P <= 32 parts; thr in metres, finite, >= 0.
+ *       counts[b][k] = number of vertices v with part[v] = k and d2[b][v] <= thr thr (float32 product);
+ *       min_d2[b][k] = the smallest d2[b][v] over part[v] = k, +inf for a part without a vertex (or
+ *                      with none in reach).
+ *   A vertex with part[v] >= P counts nowhere; a d2 that is NaN or negative is never a minimum.
+ *   Integer atomics only: a count, and a minimum on the BIT PATTERN (floats >= 0 order like unsigned
+ *   integers), accumulated in LDS per workgroup, then one atomic per workgroup and accumulator in
+ *   device memory, as mh_fit_report_pixels does it: the same bits on every launch.  Both outputs are
+ *   overwritten by the call; either may be NULL, not both.
+ * Both calls own nothing and keep nothing.                                                          */
+#define MH_SCENE_NEAREST_MAX_CELLS 32
+int mh_scene_nearest(const void* grid_ws, int M, const float* queries /*(Q,3)*/, int Q, float radius,
+                     float* d2 /*(Q)*/, float* near_xyz /*(Q,3)*/, void* stream);
+int mh_contact_parts(int B, int V, const float* d2 /*(B,V)*/, const uint8_t* part /*(V)*/, int P,
+                     float thr, int32_t* counts /*(B,P)*/, float* min_d2 /*(B,P)*/, void* stream);
+
 /* ---- stand-alone forms of losses.py:19-40 and morphology.py:6-41 (call compatibility of
  * mhmocap.losses / mhmocap.morphology; the optimiser uses the fused kernels above) --------------
  * mh_avg_depth_loss: rows = b*N maps of P pixels; `tru` has rows/group maps (group = N when the

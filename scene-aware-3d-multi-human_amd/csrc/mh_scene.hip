@@ -2,6 +2,7 @@
 // of the reference's full argsort), contact and foot-sliding residuals, scene unprojection.
 // Reference: optimizer.py:485-518 (contact / foot sliding), :605-616 + transforms.py:114-130.
 #include "mh_common.h"
+#include "mh_grid_p.h"
 
 #include <math.h>
 
@@ -417,16 +418,6 @@ extern "C" int mh_scene_unproject(const float* depth, int H, int W, const float*
 // rho * cell away).  Exactly the same neighbour set as the brute-force scan, ~50x fewer distance
 // evaluations for M = 2e4..2e5.
 // =============================================================================================
-#define GRID_MAX_CELLS (1 << 20)
-
-struct GridHdr {        // device-resident header (written by k_grid_setup)
-  float mn[3];
-  float cell;
-  int dim[3];
-  int ncells;
-  int npts;          // points in the cloud (<= the capacity the workspace was sized for)
-};
-
 __global__ __launch_bounds__(1024) void k_grid_setup(const float* pts, int M_host, const int* M_dev, GridHdr* hdr, int* counts, int max_cells) {
   __shared__ float smn[3][16], smx[3][16];
   const int M = M_dev ? *M_dev : M_host;
@@ -475,13 +466,6 @@ __global__ __launch_bounds__(1024) void k_grid_setup(const float* pts, int M_hos
   for (int i = threadIdx.x; i <= nc; i += 1024) counts[i] = 0;
 }
 
-__device__ __forceinline__ int grid_cell(const GridHdr* h, float x, float y, float z) {
-  const int cx = min(max((int)((x - h->mn[0]) / h->cell), 0), h->dim[0] - 1);
-  const int cy = min(max((int)((y - h->mn[1]) / h->cell), 0), h->dim[1] - 1);
-  const int cz = min(max((int)((z - h->mn[2]) / h->cell), 0), h->dim[2] - 1);
-  return (cz * h->dim[1] + cy) * h->dim[0] + cx;
-}
-
 __global__ void k_grid_count(const float* pts, const GridHdr* hdr, int* counts, int* pcell) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= hdr->npts) return;
@@ -526,25 +510,6 @@ __global__ void k_grid_scatter(const float* pts, const GridHdr* hdr, const int* 
   sorted[(size_t)pos * 3] = pts[(size_t)i * 3];
   sorted[(size_t)pos * 3 + 1] = pts[(size_t)i * 3 + 1];
   sorted[(size_t)pos * 3 + 2] = pts[(size_t)i * 3 + 2];
-}
-
-static size_t g_align(size_t x) { return (x + 255) & ~(size_t)255; }
-struct GridWs {
-  GridHdr* hdr;
-  int* start;     // [GRID_MAX_CELLS + 1]
-  int* cursor;    // [GRID_MAX_CELLS]
-  int* pcell;     // [M]
-  float* sorted;  // [M][3]
-};
-static GridWs grid_carve(void* ws, int M) {
-  char* c = (char*)ws;
-  GridWs g;
-  g.hdr = (GridHdr*)c; c += g_align(sizeof(GridHdr));
-  g.start = (int*)c; c += g_align((size_t)(GRID_MAX_CELLS + 1) * 4);
-  g.cursor = (int*)c; c += g_align((size_t)GRID_MAX_CELLS * 4);
-  g.pcell = (int*)c; c += g_align((size_t)M * 4);
-  g.sorted = (float*)c;
-  return g;
 }
 
 extern "C" size_t mh_scene_grid_bytes(int M) {

@@ -189,6 +189,8 @@ def lib():
         L.mh_scene_pen_term_sel.argtypes = [ctypes.c_int] * 4 + [c_float_p] + [vp] * 4 + [ctypes.c_float] * 4 + [vp] * 4
         L.mh_order_term_keys.argtypes = [ctypes.c_int] * 5 + [vp] * 6 + [ctypes.c_float] * 3 + [vp] * 6
         L.mh_order_term.argtypes = [ctypes.c_int] * 6 + [vp] * 4 + [ctypes.c_float] * 3 + [vp] * 6
+        L.mh_scene_nearest.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_float, vp, vp, vp]
+        L.mh_contact_parts.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_float, vp, vp, vp]
         L.mh_view_project.argtypes = [ctypes.c_int] * 3 + [vp, c_float_p, c_float_p, c_float_p, ctypes.c_float, vp, vp]
         L.mh_view_clear.argtypes = [ctypes.c_int] * 3 + [vp, vp]
         L.mh_view_raster.argtypes = [ctypes.c_int] * 6 + [vp] * 4

@@ -63,6 +63,7 @@ class BodyModel(object):
         assert posedirs.shape == (V, 3, 207), posedirs.shape
         J_regressor = _dense(get('J_regressor'))
         weights = _dense(get('weights'))
+        self.lbs_weights = weights                              # (V,24) on the host: mhhip.contact.body_parts
         parents = np.asarray(get('kintree_table'))[0].astype(np.int64)
         parents[0] = -1
         parents = parents.astype(np.int32)

@@ -893,6 +893,50 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         out['frames'] = idx
         return out
 
+    # -- which part of a body touches the scene (the reference has its interactive viewer to look at) ----------------------
+    def contact_map(self, frames=None, radius=0.1, contact=0.03, nearest=False, chunk=32):
+        """Per vertex, how far the current leaves put every body from the scene at ``frames`` (default: all): dict of numpy
+        arrays -- the columns of ``mhhip.contact.contact_map``, ``dist_m`` (len(frames), N, V) distance to the nearest point of
+        the scene cloud ``scene_pcd`` within ``radius`` (inf beyond it), ``contact`` the same thresholded at ``contact``,
+        ``part_verts`` / ``part_min_m`` (len(frames), N, 24) vertices in contact and smallest distance per body part
+        (``mhhip.contact.PART_NAMES``), ``contact_verts`` (len(frames), N), with ``nearest=True`` also ``nearest``
+        (len(frames), N, V, 3) the scene points themselves -- plus ``'frames'``.  The vertices are those of ``predict``; at
+        most ``chunk`` frames are on the device at a time.  Reads the leaves only: a grid and buffers of its own, nothing of
+        the engine's state is written."""
+        from mhhip import contact as mhcontact
+        if self.engine is None:
+            raise RuntimeError('contact_map: nothing to measure before init_optimized_variables()')
+        if self._world()[0] > 1:
+            raise RuntimeError('contact_map is not available in a frame-sharded run (world > 1): measure on the gathered '
+                               'result of get_optimized_variables() in one process')
+        if self.scene_pcd is None or int(self.scene_pcd.numel()) == 0:
+            raise RuntimeError('contact_map needs a scene: hand one in with update_scene_pointcloud(scene_depth, scene_mask), or '
+                               "run fit() with scene_update='device' for more than 30 cycles")
+        e = self.engine
+        T, N = self.num_frames, self.num_people
+        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
+        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
+            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
+        idx = idx.astype(np.int64)
+        chunk = max(1, int(chunk))
+        m = self.SMPLPY.body_model
+        cloud = self.scene_pcd.view(-1, 3)
+        parts = []
+        with torch.cuda.device(self.device), torch.no_grad():
+            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
+            for f0 in range(0, len(idx), chunk):
+                cur = torch.as_tensor(idx[f0:f0 + chunk], device=self.device)
+                nb = len(cur) * N
+                verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[cur].reshape(nb, 72), e.leaf('xscale').view(N),
+                                               pT_all[cur].reshape(nb, 3), want_vposed=False)
+                got = mhcontact.contact_map(m, verts.view(len(cur), N, -1, 3), cloud, radius=radius, contact=contact, nearest=nearest,
+                                            chunk=chunk)
+                parts.append({k: v.cpu().numpy() for k, v in got.items()})
+                del verts, got
+        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+        out['frames'] = idx
+        return out
+
     # -- reference optimizer.py:664-675 ---------------------------------------------------------------
     def one_euro_filter(self, x, min_cutoff=0.1, beta=0.02, frame_rate=25):
         x = torch.as_tensor(x).detach().to(self.device).float()
