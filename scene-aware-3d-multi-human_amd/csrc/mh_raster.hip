@@ -38,10 +38,19 @@
 #define BLUR_S 2e-5f         // optimizer.py:223
 #define SIGMA_S 1e-4f        // BlendParams.sigma default used by SoftSilhouetteShader
 #ifndef RB
-#define RB 512               // threads per strip workgroup
+#define RB 512               // threads per workgroup of k_raster_sums
+#endif
+// Threads per tile workgroup of the selection kernel (k_raster_strip) and the waves per SIMD its code is scheduled for.
+// The kernel fits 96 VGPRs without scratch at RSB = 640 (a fifth wave per SIMD: two workgroups of ten waves per CU), but ten
+// waves do not spread evenly over four SIMDs and the launch then runs 458 us instead of 332: measured and not
+// taken.  Eight waves it stays, two workgroups per CU by LDS, four waves per SIMD -- but SCHEDULED for five: hipcc then keeps
+// the loads of the gather pipeline close to their uses instead of spending the 128-register budget on hoisting them (101
+// VGPRs either way, no scratch), and the launch is 306 us against 317 us scheduled for four (same box).
+#ifndef RSB
+#define RSB 512
 #endif
 #ifndef RMINW
-#define RMINW 4
+#define RMINW 5
 #endif
 // window pixels per tile (5 x u64 each = 28 KB of LDS; 2 workgroups per CU).  Larger tiles = fewer of them: less work repeated
 // for the faces that reach across tiles, more rounds per wave and tile; but the selection kernel shares its CUs' LDS with the
@@ -49,6 +58,13 @@
 // with 512 entries (rounds 2-4) 0.679 and 0.669 on a second box, 704 / 384 0.670 and 0.658, 704 / 256 0.671, 768 / 384 0.665,
 // 800 / 512 0.667 (kernel alone 333 us instead of 357: the side branch then waits for LDS), 1408 px in 1024-thread
 // workgroups 0.725.
+// LDS budget of a CU (163 840 B): two tile workgroups of 68 144 B leave 27 552 B for the side branch's kernels beside them
+// (code objects: k_kp_p 16 384, k_kp_gf 16 384, k_kp_mid 15 232, k_contact_knn_grid 2 064, k_contact_foot 1 028,
+// k_filtered_verts 1 024): one key-point workgroup and the small ones.  Ten-wave workgroups (RSB = 640) need 77 440 B and
+// leave 8 960 B; with R_CAP 640 and RPL 320 they need 73 344 B, and one key-point workgroup fits again.  Swept at ten waves
+// on one box (ms per cycle; eight waves 0.655 before the register diet, 0.637 after it): R_CAP / RPL 704 / 384 0.782,
+// 704 / 320 0.789, 704 / 264 0.803, 640 / 384 0.789, 640 / 320 0.799, 640 / 264 0.813 (RPL >= 258: the even split's tables) --
+// no setting helps: the ten-wave workgroups do not share a CU at all (see RSB).
 #ifndef R_CAP
 #define R_CAP 704
 #endif
@@ -802,8 +818,7 @@ __global__ __launch_bounds__(RLISTS) void k_raster_lists(RasterP p) { r_finalize
 // needed -- no face gathers -- so this rides in the epilogue of k_raster_strip; the silhouette sum needs alpha and is taken
 // where alpha is evaluated anyway (k_raster_grads; k_raster_sums when no gradients are requested)
 __device__ __forceinline__ void r_tile_depth_sums(const RasterP& p, int s, int b, const unsigned long long* keys, int tw, int x0, int sy0,
-                                                  int npx, float* sh) {
-  const int tid = threadIdx.x;
+                                                  int npx, float* sh, const int tid) {
   const int W = p.W, P = p.H * W;
   const int t = b / p.N, n = b % p.N;
   const float min_z = logf(1.f + expf(p.zmin_lin[t]));                    // optimizer.py:683-688
@@ -811,7 +826,7 @@ __device__ __forceinline__ void r_tile_depth_sums(const RasterP& p, int s, int b
   const float inv_min = 1.f / min_z, inv_max = 1.f / max_z, dspan = inv_min - inv_max;
   const float pvalid = p.p2d_valid[b];
   float lA = 0.f, lB = 0.f, lC = 0.f, lS1 = 0.f, lS2 = 0.f;
-  for (int i = tid; i < npx; i += RB) {
+  for (int i = tid; i < npx; i += RSB) {
     const unsigned long long k0 = keys[(size_t)i * 5];
     if (k0 == RS_EMPTY) continue;
     const int yi = sy0 + i / tw, xi = x0 + i % tw;
@@ -842,13 +857,13 @@ __device__ __forceinline__ void r_tile_depth_sums(const RasterP& p, int s, int b
   __syncthreads();
   if (tid < 5) {
     float a = 0.f;
-    for (int w = 0; w < RB / 64; ++w) a += sh[w * 5 + tid];
+    for (int w = 0; w < RSB / 64; ++w) a += sh[w * 5 + tid];
     p.partial[(size_t)s * 6 + tid] = a;
   }
   if (tid == 5) p.partial[(size_t)s * 6 + 5] = 0.f;
 }
 
-#define RW (RB / 64)         // waves per tile workgroup
+#define RW (RSB / 64)         // waves per tile workgroup
 #ifndef R_KEYS_NT
 #define R_KEYS_NT 1
 #endif
@@ -867,7 +882,9 @@ __device__ __forceinline__ void r_tile_depth_sums(const RasterP& p, int s, int b
 // split evenly over the 64 lanes (every lane walks a contiguous run of pairs, the staged face stays in registers
 // while the run stays inside one face).  The run start -> face lookup is a scatter + prefix-max instead of a
 // search.  Only the key window is shared by the waves (LDS atomics).
-__global__ __launch_bounds__(RB, RMINW) void k_raster_strip(RasterP p) {       // 4 waves/SIMD: two workgroups per CU
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wpass-failed"      // "desired occupancy was 5, final occupancy is 4": by LDS, on purpose (RMINW)
+__global__ __launch_bounds__(RSB, RMINW) void k_raster_strip(RasterP p) {      // 4 waves/SIMD: two workgroups per CU
   __shared__ unsigned long long keys[R_CAP * 5];
   __shared__ float wT[RW][64 * RT];         // staged faces of the wave's current round
   __shared__ int wDesc[RW][64];             // xa | ya << 10 | nx << 20 (tile-relative)
@@ -877,9 +894,9 @@ __global__ __launch_bounds__(RB, RMINW) void k_raster_strip(RasterP p) {       /
   // coordinates share one array (columns + rows <= pixels + 1): LDS the side branch's kernels can have
   static_assert(RPL * 2 >= (65 + 64) * 4, "the pair list must cover the even-split path's tables");
   __shared__ __attribute__((aligned(8))) unsigned short wPl[RW][RPL];
-  __shared__ float s_sums[RB / 64 * 5];
+  __shared__ float s_sums[RSB / 64 * 5];
   __shared__ float sXY[R_CAP + 2];          // NDC x of the tile's columns, then NDC y of its rows
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = p.H, W = p.W;
   const float blur_d = sqrtf(BLUR_D);
   const int total = p.total[0];
@@ -929,9 +946,13 @@ __global__ __launch_bounds__(RB, RMINW) void k_raster_strip(RasterP p) {       /
     const unsigned* fs = p.fsort + (size_t)b * p.F;
     const int* rs = p.row_start + (size_t)b * (4 * (H + 1) + 1);
     __syncthreads();
-    for (int i = tid; i < npx * 5; i += RB) keys[i] = RS_EMPTY;
-    for (int i = tid; i < tw; i += RB) sXf[i] = r_pix_to_ndc(W - 1 - (x0 + i), W, H);
-    for (int i = tid; i < nrows; i += RB) sYf[i] = r_pix_to_ndc(H - 1 - (sy0 + i), H, W);
+    // the thread index of the tile's prologue and epilogue, opaque to the compiler: the loops' strength-reduced addresses
+    // (a dozen registers) would otherwise be computed once per kernel and held across every round
+    int ti = tid;
+    asm volatile("" : "+v"(ti));
+    for (int i = ti; i < npx * 5; i += RSB) keys[i] = RS_EMPTY;
+    for (int i = ti; i < tw; i += RSB) sXf[i] = r_pix_to_ndc(W - 1 - (x0 + i), W, H);
+    for (int i = ti; i < nrows; i += RSB) sYf[i] = r_pix_to_ndc(H - 1 - (sy0 + i), H, W);
     // candidate faces: the near class of the rows first, then the far class (two contiguous ranges of fsort)
     // three contiguous ranges of fsort: near short faces, far short faces, tall faces.  Kept lists: a face's first row may
     // have moved by up to `margin` rows either way since the sort
@@ -946,7 +967,8 @@ __global__ __launch_bounds__(RB, RMINW) void k_raster_strip(RasterP p) {       /
     R_TMARK(0);
     if (i1 > 0) {
       const int last = i1 - 1, stride = RW * 64;
-      int idx = wave * 64 + lane;
+      int base = wave * 64;                  // wave-uniform: the loop below is a scalar loop
+      int idx = base + lane;
       // pipeline registers: entry of round r+2, vertex ids of round r+1, coordinates of round r
       unsigned e_a = fs_at(min(idx, last)), e_b = fs_at(min(idx + stride, last)), e_c = fs_at(min(idx + 2 * stride, last));
       int va[3], vb_[3];
@@ -960,7 +982,7 @@ __global__ __launch_bounds__(RB, RMINW) void k_raster_strip(RasterP p) {       /
         const unsigned o = __umul24((unsigned)va[k], 3u);        // 32-bit offsets: SGPR base + VGPR offset loads
         ca[3 * k] = nb[o]; ca[3 * k + 1] = nb[o + 1u]; ca[3 * k + 2] = nb[o + 2u];
       }
-      for (; idx - lane < i1; idx += stride) {
+      for (; base < i1; base += stride, idx += stride) {
         // ---- issue the next rounds' gathers before working on this one ------------------------------------
         const unsigned e_n = fs_at(min(idx + 3 * stride, last));
         int vn[3];
@@ -1173,25 +1195,27 @@ __global__ __launch_bounds__(RB, RMINW) void k_raster_strip(RasterP p) {       /
     R_TMARK(1);
     __syncthreads();
     R_TMARK(5);
+    int te = tid;
+    asm volatile("" : "+v"(te));
     // finished tile -> HBM (40 B per pixel), window row-major
     const int wx0 = p.win[b * 4], wy0 = p.win[b * 4 + 1], ww = p.win[b * 4 + 2];
     unsigned long long* gk = p.gkeys + (size_t)p.body_koff[b] * 5;
     if (tw == ww && x0 == wx0) {   // a full-width strip of rows (the usual tiling) is one contiguous range of the body's keys
       unsigned long long* dst = gk + (size_t)(sy0 - wy0) * ww * 5;
 #if R_KEYS_NT       // written once, read a kernel later: kept out of the L2 sets the other tiles' gathers live in (-6 us same-box)
-      for (int i = tid; i < npx * 5; i += RB) __builtin_nontemporal_store(keys[i], dst + i);
+      for (int i = te; i < npx * 5; i += RSB) __builtin_nontemporal_store(keys[i], dst + i);
 #else
-      for (int i = tid; i < npx * 5; i += RB) dst[i] = keys[i];
+      for (int i = te; i < npx * 5; i += RSB) dst[i] = keys[i];
 #endif
     } else {
-      for (int i = tid; i < npx * 5; i += RB) {
+      for (int i = te; i < npx * 5; i += RSB) {
         const int px = i / 5, c = i - px * 5;
         const int r = px / tw, cc = px - r * tw;
         gk[((size_t)(sy0 - wy0 + r) * ww + (x0 - wx0 + cc)) * 5 + c] = keys[i];
       }
     }
-    if (tid == 0) p.kvalid[b] = 1;               // the body has keys: its next face sort finds its winners
-    r_tile_depth_sums(p, s, b, keys, tw, x0, sy0, npx, s_sums);
+    if (te == 0) p.kvalid[b] = 1;               // the body has keys: its next face sort finds its winners
+    r_tile_depth_sums(p, s, b, keys, tw, x0, sy0, npx, s_sums, te);
     R_TMARK(6);
   }
 #ifdef MH_EXPERIMENT_TIMING
@@ -1214,6 +1238,7 @@ __global__ __launch_bounds__(RB, RMINW) void k_raster_strip(RasterP p) {       /
   }
 #endif
 }
+#pragma clang diagnostic pop
 
 // =============================================================================================
 // residual sums per strip (optimizer.py:432-442, 447-477)
@@ -2111,7 +2136,7 @@ static int raster_terms_impl(int T, int N, int V, int F, int H, int W, const flo
   // persistent grids over the device-side work list (the strip count is only known on the device)
   const int grid = R_STRIP_GRID;
   mh_prof_mark(MH_PROF_RASTER_STRIP, 0, st);
-  hipLaunchKernelGGL(k_raster_strip, dim3(grid), dim3(RB), 0, st, p);
+  hipLaunchKernelGGL(k_raster_strip, dim3(grid), dim3(RSB), 0, st, p);
   MH_LAUNCH_CHECK();
   mh_prof_mark(MH_PROF_RASTER_STRIP, 1, st);
   if (!gverts || zbuf_out || alpha_out) {   // values only (render, loss evaluation) or images wanted: alpha is evaluated by k_raster_sums
