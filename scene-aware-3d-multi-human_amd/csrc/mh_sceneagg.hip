@@ -429,7 +429,7 @@ static int scene_fill_launch(int H, int W, int ksize, int truncate, float* depth
   case KS:                                                                                                                 \
     hipLaunchKernelGGL((k_scene_fill<KS, NP, NT>), dim3(1), dim3(NT), 0, st, H, W, truncate, depth, mask, list_a, list_b, upd); \
     break;
-  switch (ksize | 1) {      // an even size covers the same pixels as the next odd one minus a row/column: not used by the reference
+  switch (ksize | 1) {      // an even size covers exactly the pixels of the next odd one (k = size / 2 on both sides, utils.py:117)
     FILL_CASE(3, 16, 1024)
     FILL_CASE(5, 32, 1024)
     FILL_CASE(7, 64, 1024)
