@@ -952,6 +952,94 @@ int mh_scene_nearest(const void* grid_ws, int M, const float* queries /*(Q,3)*/,
 int mh_contact_parts(int B, int V, const float* d2 /*(B,V)*/, const uint8_t* part /*(V)*/, int P,
                      float thr, int32_t* counts /*(B,P)*/, float* min_d2 /*(B,P)*/, void* stream);
 
+/* ---- person-to-person contact map: the nearest OTHER body of every vertex ---------------------------
+ * The one 3D result between people: do two people touch, where, with which body parts, and on which
+ * side of the other's surface a vertex lies (the depth-ordering term and its report work in image
+ * space, per pixel; the reference answers this through its interactive viewer only).  Read-only, off
+ * the cycle; no term of the fit.  All arithmetic below is float32, every operation rounded on its
+ * own, in exactly the order written, with no fused multiply-add: a float32 evaluation of the same
+ * expressions on the host gives the same bits.  No float atomics anywhere: the same bits on every
+ * launch.
+ *
+ * mh_vertex_normals: area-weighted, NOT normalised vertex normals of B bodies with the same F faces.
+ *   adj_start (V+1), adj_face (A): for vertex v the faces adj_face[adj_start[v] .. adj_start[v+1]-1]
+ *   that name it (mhhip.proximity.vertex_faces builds the table: ascending face index, a face once
+ *   per corner that names the vertex).
+ *       normals[b][v] = sum over k = adj_start[v] .. adj_start[v+1]-1, IN THAT ORDER, starting from
+ *                       +0, of n(f), f = adj_face[k];
+ *       with (v0, v1, v2) the vertices of face f, e1 = v1 - v0, e2 = v2 - v0:
+ *       n(f) = (e1.y e2.z - e1.z e2.y,  e1.z e2.x - e1.x e2.z,  e1.x e2.y - e1.y e2.x).
+ *   Only the direction is used, and leaving out the square root and the division keeps the bits
+ *   reproducible.  A gather, one lane per (body, vertex).  A face index outside [0, F), or a face
+ *   that names a vertex outside [0, V), contributes nothing (the range k is clipped to [0, A]); a
+ *   vertex without faces gets (0, 0, 0).
+ *   Refused before any HIP call: B, V or F <= 0, A < 0, B * V beyond one launch, a NULL pointer
+ *   (adj_face may be NULL when A = 0).
+ *
+ * mh_person_nearest: verts (T,N,V,3) on the device: N bodies of V vertices in each of T frames;
+ *   live (T,N) uint8 or NULL; radius in metres; ws: a workspace of at least
+ *   mh_person_nearest_bytes(T, N, V) bytes, whose content before and after the call means nothing.
+ *   A person n of frame t is LIVE iff live is NULL or live[t][n] != 0.
+ *   For query q = verts[t][n][v] of a live person with three finite coordinates, the candidates are
+ *   the p = verts[t][m][u] with m != n in the SAME frame, m live and p of three finite coordinates,
+ *       dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;   d2 = (dx dx + dy dy) + dz dz;
+ *       r2 = radius radius;   d2 <= r2   (a NaN d2 is no candidate).
+ *   d2[t][n][v] = the smallest candidate d2; idx[t][n][v] = m V + u of the candidate that attains
+ *   it, on equal d2 the smallest m, then the smallest u.  Without a candidate, for a dead person and
+ *   for a query that is not finite: d2 = +inf, idx = -1.  The result is a function of the candidate
+ *   SET, not of any visiting order.  Either output may be NULL, not both.
+ *   One uniform grid per BODY (at most 4096 cells, cell >= 0.02 m), all built by four launches over
+ *   the call (boxes, counts, scan, scatter; integer atomics only); vertices that are not finite are
+ *   neither binned nor do they widen a box; a body of zero extent is one cell.  The query is one
+ *   lane per vertex that walks the other bodies of its frame and drops a body whose bounding box,
+ *   grown by the radius, misses it after reading that body's header; in the others it walks the
+ *   rows of cells its box [q - r, q + r] can touch, a superset of every candidate's cell under
+ *   float32 rounding (csrc/mh_proximity.hip argues it).
+ *   Refused before any HIP call: T, N or V <= 0; N > 32; N V >= 2^31; T N V beyond what one launch
+ *   can index; NULL verts or ws; ws_bytes below mh_person_nearest_bytes; both outputs NULL; a radius
+ *   that is not finite and positive, or above 0.64 m (the cap of mh_scene_nearest).
+ *
+ * mh_person_pairs: d2, idx (T,N,V) as mh_person_nearest wrote them for verts; normals (T,N,V,3) as
+ *   mh_vertex_normals wrote them for verts, or NULL; part (V) uint8, the part of every vertex, the
+ *   same for all bodies; P <= 32 parts; thr in metres, finite, >= 0.
+ *   For vertex v of person n with idx = m V + u >= 0, q = verts[t][n][v], p = verts[t][m][u]:
+ *       IN CONTACT iff d2 <= thr thr (float32 product);
+ *       BEHIND iff normals is given and, with w = normals[t][m][u],
+ *           ((q.x - p.x) w.x + (q.y - p.y) w.y) + (q.z - p.z) w.z < 0.
+ *   BEHIND says that the vertex lies on the inner side of the other body's surface AT THAT BODY'S
+ *   NEAREST VERTEX: a cheap, local stand-in for "inside", exact in its definition.  It is NOT a
+ *   winding-number (points-inside-mesh) test and can differ from one near concave regions.
+ *       behind[t][n][v]      = 1 iff the vertex is behind, in contact or not; 0 where idx < 0;
+ *       pair_verts[t][n][m]  = vertices of n in contact whose nearest person is m;
+ *       pair_behind[t][n][m] = vertices of n in contact and behind whose nearest person is m;
+ *       pair_min_d2[t][n][m] = the smallest d2 over the vertices of n whose nearest person is m,
+ *                              +inf when there is none (the diagonal is 0 / +inf);
+ *       part_verts[t][n][k]  = vertices in contact with part[v] = k;
+ *       part_min_key[t][n][k] = the 64-bit minimum over part[v] = k, idx >= 0 of
+ *                              (bits of d2 << 32 | idx), all ones when there is none: one integer
+ *                              gives the part's smallest distance and the vertex of the other body it
+ *                              is closest to (on equal d2 the smallest idx).
+ *   A part[v] >= P counts nowhere; an idx at or beyond N V is treated as idx < 0; a d2 that is NaN
+ *   or negative is never a minimum.  Integer atomics only -- counts, and minima on the BIT PATTERN
+ *   (floats >= 0 order like unsigned integers) -- accumulated in LDS per workgroup, then one atomic
+ *   per workgroup and accumulator in device memory, as mh_contact_parts does it.  V need not be a
+ *   multiple of the workgroup.  Every output is overwritten by the call; each may be NULL, not all.
+ *   Refused before any HIP call: T, N or V <= 0; N > 32; P outside 1..32; N V >= 2^31; T N V beyond
+ *   one launch; NULL verts, d2, idx or part; every output NULL; thr not finite or negative.
+ * The calls own nothing and keep nothing.                                                           */
+int mh_vertex_normals(int B, int V, int F, const float* verts /*(B,V,3)*/, const int32_t* faces /*(F,3)*/,
+                      const int32_t* adj_start /*(V+1)*/, const int32_t* adj_face /*(A)*/, int A,
+                      float* normals /*(B,V,3)*/, void* stream);
+size_t mh_person_nearest_bytes(int T, int N, int V);
+int mh_person_nearest(int T, int N, int V, const float* verts /*(T,N,V,3)*/, const uint8_t* live /*(T,N)*/,
+                      float radius, void* ws, size_t ws_bytes, float* d2 /*(T,N,V)*/,
+                      int32_t* idx /*(T,N,V)*/, void* stream);
+int mh_person_pairs(int T, int N, int V, const float* verts, const float* normals /*(T,N,V,3)*/,
+                    const float* d2, const int32_t* idx, const uint8_t* part /*(V)*/, int P, float thr,
+                    uint8_t* behind /*(T,N,V)*/, int32_t* pair_verts /*(T,N,N)*/,
+                    float* pair_min_d2 /*(T,N,N)*/, int32_t* pair_behind /*(T,N,N)*/,
+                    int32_t* part_verts /*(T,N,P)*/, uint64_t* part_min_key /*(T,N,P)*/, void* stream);
+
 /* ---- stand-alone forms of losses.py:19-40 and morphology.py:6-41 (call compatibility of
  * mhmocap.losses / mhmocap.morphology; the optimiser uses the fused kernels above) --------------
  * mh_avg_depth_loss: rows = b*N maps of P pixels; `tru` has rows/group maps (group = N when the

@@ -191,6 +191,11 @@ def lib():
         L.mh_order_term.argtypes = [ctypes.c_int] * 6 + [vp] * 4 + [ctypes.c_float] * 3 + [vp] * 6
         L.mh_scene_nearest.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_float, vp, vp, vp]
         L.mh_contact_parts.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_float, vp, vp, vp]
+        L.mh_vertex_normals.argtypes = [ctypes.c_int] * 3 + [vp] * 4 + [ctypes.c_int, vp, vp]
+        L.mh_person_nearest_bytes.restype = ctypes.c_size_t
+        L.mh_person_nearest_bytes.argtypes = [ctypes.c_int] * 3
+        L.mh_person_nearest.argtypes = [ctypes.c_int] * 3 + [vp, vp, ctypes.c_float, vp, ctypes.c_size_t, vp, vp, vp]
+        L.mh_person_pairs.argtypes = [ctypes.c_int] * 3 + [vp] * 5 + [ctypes.c_int, ctypes.c_float] + [vp] * 7
         L.mh_view_project.argtypes = [ctypes.c_int] * 3 + [vp, c_float_p, c_float_p, c_float_p, ctypes.c_float, vp, vp]
         L.mh_view_clear.argtypes = [ctypes.c_int] * 3 + [vp, vp]
         L.mh_view_raster.argtypes = [ctypes.c_int] * 6 + [vp] * 4

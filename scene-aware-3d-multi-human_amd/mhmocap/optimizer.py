@@ -937,6 +937,49 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         out['frames'] = idx
         return out
 
+    # -- which people touch, where and with which parts (again the reference has its viewer only) --------------------------
+    def proximity_map(self, frames=None, radius=0.1, contact=0.02, nearest=False, chunk=8):
+        """Per vertex, how far the current leaves put every body from the OTHER people of its frame at ``frames`` (default:
+        all): dict of numpy arrays -- the columns of ``mhhip.proximity.proximity_map``: ``dist_m`` (len(frames), N, V) distance
+        to the nearest vertex of another person within ``radius`` (inf beyond it), ``contact`` the same thresholded at
+        ``contact``, ``behind`` the local side test against that vertex's normal, ``other`` the other person, the per-pair
+        tables ``pair_verts`` / ``pair_behind`` / ``pair_min_m`` (len(frames), N, N), the per-part tables ``part_verts`` /
+        ``part_min_m`` / ``part_other`` / ``part_other_part`` (len(frames), N, 24), ``contact_verts`` / ``behind_verts``
+        (len(frames), N), with ``nearest=True`` also ``other_vert`` and ``nearest`` -- plus ``'frames'``.  The vertices are
+        those of ``predict``; a person counts where the fit's thresholded ``valid_smpl`` says it is there; at most ``chunk``
+        frames are on the device at a time.  Needs no scene and no staged images.  Reads the leaves only: a workspace and
+        buffers of its own, nothing of the engine's state is written."""
+        from mhhip import proximity as mhprox
+        if self.engine is None:
+            raise RuntimeError('proximity_map: nothing to measure before init_optimized_variables()')
+        if self._world()[0] > 1:
+            raise RuntimeError('proximity_map is not available in a frame-sharded run (world > 1): measure on the gathered '
+                               'result of get_optimized_variables() in one process')
+        e = self.engine
+        T, N = self.num_frames, self.num_people
+        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
+        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
+            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
+        idx = idx.astype(np.int64)
+        chunk = max(1, int(chunk))
+        m = self.SMPLPY.body_model
+        live = self._valid.reshape(T, N) > 0
+        parts = []
+        with torch.cuda.device(self.device), torch.no_grad():
+            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
+            for f0 in range(0, len(idx), chunk):
+                cur = torch.as_tensor(idx[f0:f0 + chunk], device=self.device)
+                nb = len(cur) * N
+                verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[cur].reshape(nb, 72), e.leaf('xscale').view(N),
+                                               pT_all[cur].reshape(nb, 3), want_vposed=False)
+                got = mhprox.proximity_map(m, verts.view(len(cur), N, -1, 3), live=live[idx[f0:f0 + chunk]], radius=radius,
+                                           contact=contact, nearest=nearest, chunk=chunk)
+                parts.append({k: v.cpu().numpy() for k, v in got.items()})
+                del verts, got
+        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+        out['frames'] = idx
+        return out
+
     # -- reference optimizer.py:664-675 ---------------------------------------------------------------
     def one_euro_filter(self, x, min_cutoff=0.1, beta=0.02, frame_rate=25):
         x = torch.as_tensor(x).detach().to(self.device).float()
