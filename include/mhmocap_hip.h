@@ -1044,7 +1044,8 @@ int mh_person_pairs(int T, int N, int V, const float* verts, const float* normal
  * mhmocap.losses / mhmocap.morphology; the optimiser uses the fused kernels above) --------------
  * mh_avg_depth_loss: rows = b*N maps of P pixels; `tru` has rows/group maps (group = N when the
  * target is (b,1,H,W)).  row_sums (rows,3) = {sum m*log(clamp pred), sum m*log(clamp true), sum m};
- * the loss is sum_r ((s0 - s1)/(s2+1))^2 (host adds rows_loss from row_sums, or reads it back).
+ * the loss is sum_r ((s0 - s1)/(s2+1))^2, which the host forms from row_sums.  row_loss must not be NULL but is
+ * neither read nor written (it may be row_sums itself): nothing on the device evaluates the per-row loss.
  * _backward: gpred (rows,P), gtrue_rows (rows,P) [caller sums the group], scaled by grad_out.      */
 int mh_avg_depth_loss(const float* pred, const float* tru, const float* mask, int rows, int group,
                       size_t P, float eps, float* row_sums, float* row_loss, void* stream);

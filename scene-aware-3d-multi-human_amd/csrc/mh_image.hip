@@ -162,6 +162,7 @@ extern "C" int mh_sil_mask_stats(const uint32_t* bits, int T, int N, int H, int 
                                  float* D, float* S, void* stream) {
   MH_CHECK(bits && pT && pose2d_valid && mask_valid && front && apply && D && S, "null argument");
   MH_CHECK(T > 0 && N > 0 && N <= 32, "need 1..32 people per frame");
+  MH_CHECK(H > 0 && W > 0, "empty image");
   const int parts = T >= 2048 ? 1 : (T >= 512 ? 4 : 8);
   MH_HIP(hipMemsetAsync(D, 0, (size_t)T * N * sizeof(float), (hipStream_t)stream));
   MH_HIP(hipMemsetAsync(S, 0, (size_t)T * N * sizeof(float), (hipStream_t)stream));
@@ -250,6 +251,7 @@ extern "C" int mh_sil_mask_stats_cached(const uint32_t* bits, int T, int N, int 
                                         float* D, float* S, int32_t* tag, void* stream) {
   MH_CHECK(bits && pT && pose2d_valid && mask_valid && front && apply && D && S && tag, "null argument");
   MH_CHECK(T > 0 && N > 0 && N <= 32, "need 1..32 people per frame");
+  MH_CHECK(H > 0 && W > 0, "empty image");
 #define SIL_LAUNCH(NM) hipLaunchKernelGGL(k_sil_stats_cached<NM>, dim3(T), dim3(256), 0, (hipStream_t)stream, bits, N, \
                                           H * W, pT, pose2d_valid, mask_valid, front, apply, D, S, tag)
   if (N <= 4) SIL_LAUNCH(4);
@@ -515,6 +517,7 @@ extern "C" int mh_masked_mse(const float* a, const float* b, const float* mask, 
 extern "C" int mh_masked_mse_backward(const float* a, const float* b, const float* mask, size_t n, const float* sums2,
                                       float grad_out, float* ga, void* stream) {
   MH_CHECK(a && b && mask && sums2 && ga, "null argument");
+  MH_CHECK(n > 0, "empty input");
   const size_t nb = (n + 255) / 256;
   hipLaunchKernelGGL(k_mse_grad, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, (hipStream_t)stream, a, b, mask, n, sums2,
                      grad_out, ga);

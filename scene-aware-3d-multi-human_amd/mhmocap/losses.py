@@ -45,26 +45,42 @@ class _MaskedMse(torch.autograd.Function):
         a, b, m = y1.contiguous().float(), y2.expand_as(y1).contiguous().float(), mask.expand_as(y1).contiguous().float()
         sums = torch.empty(2, dtype=torch.float32, device=a.device)
         check(_lib.lib().mh_masked_mse(ptr(a), ptr(b), ptr(m), a.numel(), ptr(sums), _lib.stream_ptr(a.device)))
+        if mask.numel() != a.numel():
+            # losses.py:36 counts the mask as it was handed in, not as it broadcasts against y1 - y2
+            m0 = mask.contiguous().float()
+            check(_lib.lib().mh_reduce_sum(ptr(m0), m0.numel(), 1.0, sums.data_ptr() + 4, _lib.stream_ptr(a.device)))
         ctx.save_for_backward(a, b, m, sums)
+        ctx.shapes = (y1.shape, y2.shape)
         return sums[0] / (sums[1] + 1.0)
 
     @staticmethod
     def backward(ctx, gout):
         a, b, m, sums = ctx.saved_tensors
+        s1, s2 = ctx.shapes
         ga = torch.empty_like(a)
         check(_lib.lib().mh_masked_mse_backward(ptr(a), ptr(b), ptr(m), a.numel(), ptr(sums), float(gout), ptr(ga),
                                                 _lib.stream_ptr(a.device)))
-        return ga, None, None
+        # the loss is a function of y1 - y2 (losses.py:37): the second argument's gradient is the first one's negated,
+        # summed over the dimensions y2 was broadcast along
+        g2 = (-ga).sum_to_size(s2) if ctx.needs_input_grad[1] else None
+        return (ga.view(s1) if ctx.needs_input_grad[0] else None), g2, None
+
+
+def _no_mask_gradient(mask):
+    if torch.is_tensor(mask) and mask.requires_grad:
+        raise ValueError('the mask requires grad: the HIP losses have no gradient for it (detach the mask)')
 
 
 def build_avg_depth_loss_fn(eps=1e-3):
     def _depth_loss_fn(y_pred, y_true, mask):
+        _no_mask_gradient(mask)
         return _AvgDepthLoss.apply(y_pred, y_true, mask, eps)
     return _depth_loss_fn
 
 
 def build_masked_mse_loss_fn():
     def _masked_mse_loss_fn(y1, y2, mask):
+        _no_mask_gradient(mask)
         return _MaskedMse.apply(y1, y2, mask)
     return _masked_mse_loss_fn
 

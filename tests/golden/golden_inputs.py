@@ -124,3 +124,61 @@ def fit_raster_inputs(gr):
                 backmasks=gr['in_backmasks'].astype(np.int64), poses_smpl=gr['in_poses_smpl'],
                 betas_smpl=gr['in_betas_smpl'], valid_smpl=gr['in_valid_smpl'], trans_gt=gr['in_trans_gt'],
                 scene_depth=gr['in_scene_depth'], scene_mask=gr['in_scene_mask'] > 0)
+
+
+# ---- inputs of make_golden_image.py (tests/golden/reference_image_cpu.npz) ---------------------------------------------------
+IMAGE_MORPH_KSIZES = (1, 3, 5, 7)
+IMAGE_MORPH_SIZES = ((1, 1), (1, 7), (5, 1), (2, 2), (6, 9))
+
+
+def image_morph_inputs():
+    """{(H, W): (2, 1, H, W) float32 maps} with values below, just below, at and above the 0.5 threshold"""
+    half = np.float32(0.5)
+    vals = np.array([0.0, np.nextafter(half, np.float32(0), dtype=np.float32), 0.5, 0.7, 1.0, 1.0, 1.0, 1.0], np.float32)
+    out = {}
+    for H, W in IMAGE_MORPH_SIZES:
+        rng = np.random.RandomState(1400 + 10 * H + W)
+        out[(H, W)] = vals[rng.randint(0, 8, (2, 1, H, W))]
+    return out
+
+
+def _image_clamp_edges(x, at):
+    """four consecutive pixels of every map: just below eps = 1e-3, exactly float32(eps), zero, negative"""
+    e = np.float32(1e-3)
+    flat = x.reshape(x.shape[0], x.shape[1], -1)
+    flat[..., at:at + 4] = np.array([np.nextafter(e, np.float32(0), dtype=np.float32), e, 0.0, -0.25], np.float32)
+
+
+def image_depth_loss_cases():
+    """{name: (pred (b,N,H,W), true (b,1|N,H,W), mask (b,1|N,H,W))}: every pairing of a shared / per-person target with a
+    shared / per-person mask; pixels below eps, at eps, zero and negative in both arguments; the last case has a mask
+    that is not binary"""
+    b, N, H, W = 2, 3, 5, 7
+    out = {}
+    for i, (tn, mn) in enumerate([(1, 1), (1, N), (N, 1), (N, N)]):
+        rng = np.random.RandomState(1500 + i)
+        pred = rng.uniform(0.05, 1.0, (b, N, H, W)).astype(np.float32)
+        true = rng.uniform(0.05, 1.0, (b, tn, H, W)).astype(np.float32)
+        mask = (rng.rand(b, mn, H, W) > 0.4).astype(np.float32)
+        _image_clamp_edges(pred, 3)
+        _image_clamp_edges(true, 9)
+        mask.reshape(b, mn, -1)[..., 3:13] = 1
+        out['t%d_m%d' % (tn, mn)] = (pred, true, mask)
+    pred, true, mask = out['t1_m%d' % N]
+    rng = np.random.RandomState(1510)
+    out['soft_mask'] = (pred, true, (mask * rng.uniform(0.2, 1.0, mask.shape)).astype(np.float32))
+    return out
+
+
+def image_mse_cases():
+    """{name: (y1, y2, mask)}: all three of one shape; the second argument and the mask broadcast (along different
+    dimensions); a mask that is not binary"""
+    b, N, H, W = 2, 3, 5, 7
+    rng = np.random.RandomState(1600)
+    y1 = rng.uniform(0, 1, (b, N, H, W)).astype(np.float32)
+    y2 = rng.uniform(0, 1, (b, N, H, W)).astype(np.float32)
+    mask = (rng.rand(b, N, H, W) > 0.4).astype(np.float32)
+    soft = (mask * rng.uniform(0.2, 1.0, mask.shape)).astype(np.float32)
+    return {'full': (y1, y2, mask),
+            'broadcast': (y1, y2[:, :1].copy(), mask[:1, :, :, :1].copy()),
+            'soft_mask': (y1, y2[:1].copy(), soft)}
