@@ -1008,7 +1008,8 @@ int mh_contact_parts(int B, int V, const float* d2 /*(B,V)*/, const uint8_t* par
  *           ((q.x - p.x) w.x + (q.y - p.y) w.y) + (q.z - p.z) w.z < 0.
  *   BEHIND says that the vertex lies on the inner side of the other body's surface AT THAT BODY'S
  *   NEAREST VERTEX: a cheap, local stand-in for "inside", exact in its definition.  It is NOT a
- *   winding-number (points-inside-mesh) test and can differ from one near concave regions.
+ *   winding-number (points-inside-mesh) test and can differ from one near concave regions
+ *   (mh_person_inside below is that test).
  *       behind[t][n][v]      = 1 iff the vertex is behind, in contact or not; 0 where idx < 0;
  *       pair_verts[t][n][m]  = vertices of n in contact whose nearest person is m;
  *       pair_behind[t][n][m] = vertices of n in contact and behind whose nearest person is m;
@@ -1039,6 +1040,99 @@ int mh_person_pairs(int T, int N, int V, const float* verts, const float* normal
                     uint8_t* behind /*(T,N,V)*/, int32_t* pair_verts /*(T,N,N)*/,
                     float* pair_min_d2 /*(T,N,N)*/, int32_t* pair_behind /*(T,N,N)*/,
                     int32_t* part_verts /*(T,N,P)*/, uint64_t* part_min_key /*(T,N,P)*/, void* stream);
+
+/* ---- points inside a mesh, and the person-to-person penetration map ---------------------------------
+ * Is a point INSIDE a closed triangle mesh, and how far is the surface above and below it along z
+ * (the camera axis): the winding-number test that BEHIND above is not.  Read-only, off the cycle; no
+ * term of the fit.  The test is defined in integers, so it is exact, the same on every launch, and an
+ * int64 evaluation of the same rules on the host gives the same bits (tests/inside_ref.py).
+ *
+ * LATTICE.  A coordinate x becomes X = (int32) rintf(x * 65536.0f): the scaling is exact, the rounding
+ *   is half to even, the step is 2^-16 m.  All later arithmetic is integer.
+ * TESTABLE BODY.  A vertex is finite iff its three coordinates are.  A body is testable iff it is
+ *   live, has at least one finite vertex, every finite coordinate of every vertex satisfies
+ *   |x| < 8192 m, and its lattice box over the finite vertices is at most 2^19 units (8 m) on every
+ *   axis.  Any other body contains nothing; its status word says why.
+ * SKIPPED FACES.  A face that names a vertex outside [0, V), or a vertex that is not finite,
+ *   contributes nothing.
+ * EDGE SIGN.  For the directed edge P0 -> P1 and the query Q, in int64,
+ *       E = (X1 - X0) (Qy - Y0) - (Y1 - Y0) (Qx - X0);
+ *       sgn = sign(E) if E != 0; else -sign(Y1 - Y0) if Y1 != Y0; else sign(X1 - X0) (0 if X1 = X0).
+ *   This is the symbolic perturbation Q + (eps, eps^2): E(Q + (eps, eps^2)) = E - eps (Y1 - Y0) +
+ *   eps^2 (X1 - X0).  It is antisymmetric under edge reversal, so a ray through a shared edge or a
+ *   vertex is counted for exactly one of the faces around it.
+ * FACE AND QUERY.  For the face (P0, P1, P2): w0 = E(P1 -> P2), w1 = E(P2 -> P0), w2 = E(P0 -> P1),
+ *   A = w0 + w1 + w2 (twice the signed area of the face's projection, whatever Q is).
+ *       The face COVERS Q iff A != 0 and the three edge signs are equal and not zero.
+ *       Nn = w0 (Z0 - Qz) + w1 (Z1 - Qz) + w2 (Z2 - Qz)     (Nn / A = the face's z over Q, minus Qz)
+ *       ABOVE iff Nn != 0 and sign(Nn) = sign(A); BELOW iff Nn != 0 and sign(Nn) != sign(A); Nn = 0
+ *       (the query is on the face) is neither.  dz = |Nn| / |A|, truncated, in lattice units.
+ *   Bounds: a query that is tested lies in the body's closed box, so every coordinate difference is
+ *   at most 2^19 in magnitude and kept in int32; |E| <= 2 * 2^38 = 2^39; |A| <= 2^38 (twice an area
+ *   inside a 2^19 square); |Nn| <= 3 * 2^39 * 2^19 < 2^61; on a covering face the w have one sign,
+ *   so |Nn| <= |A| 2^19 and dz <= 2^19.
+ * RESULTS per (query, body).
+ *       winding = the sum over covering faces ABOVE of sign(A): +1 inside an outward-oriented closed
+ *                 mesh (counter-clockwise seen from outside in a right-handed frame), -1 inside an
+ *                 inward-oriented one, 0 outside either;
+ *       up      = the smallest dz over covering faces ABOVE, down = over those BELOW; -1 without one.
+ *   A query that is not finite, or lies outside the body's closed lattice box (a query with a
+ *   coordinate at or beyond 8192 m is outside every box), has winding 0 and up = down = -1.
+ *   INSIDE iff winding != 0; exit(q, m) = the smaller of up and down that exist.  Every result is a
+ *   function of the face SET, never of a visiting order or of the search structure.
+ *
+ * mh_mesh_bins: B bodies verts (B,V,3) with the same faces (F,3); live (B) uint8 or NULL (all live).
+ *   Fills ws (at least mh_mesh_bins_bytes(B, F) bytes) for mh_mesh_winding and mh_person_inside: per
+ *   body the status, the lattice box, the three lattice corners of every face, and a 2D grid over
+ *   the box's x and y.  The cell edge is the smallest power of two (a cell index is a shift) at which
+ *   the grid has at most 64 cells per axis and at most max(F / 4, 256) cells in all; a face is listed
+ *   in every cell its closed xy box overlaps (count, scan, fill; integer atomics only), so a query
+ *   looks at the one cell it falls in.  The lists of a body hold at most 8 F entries; a body that
+ *   needs more is marked and its queries walk all F faces -- coarse meshes of a dozen huge faces are
+ *   the ones that take that path.  The results are the same either way.
+ *   status[b] (may be NULL): bit 1 = not live, 2 = live but not testable (the range rules above),
+ *   4 = testable and walking all faces.  A body contains nothing iff status & 3.
+ *   mh_mesh_set_all_faces(1) sends every testable body of later mh_mesh_bins calls down the
+ *   all-faces path (a yardstick for what the grid buys, and a test of the claim above); it returns
+ *   the previous setting, and 0 restores the default.
+ *   Refused before any HIP call: B, V or F <= 0; B V or 8 B F beyond one launch; NULL verts, faces or
+ *   ws; ws_bytes below mh_mesh_bins_bytes.
+ * mh_mesh_winding: the generic query, points (B,Q,3): point j of row b against body b of the ws that
+ *   mh_mesh_bins filled for the same B, V, F and faces.  One lane per point.  winding, up, down (B,Q)
+ *   int32; each may be NULL, not all.
+ *   Refused before any HIP call: B, V, F or Q <= 0; B Q or 8 B F beyond one launch; NULL faces, ws or
+ *   points; every output NULL.
+ * mh_person_inside: verts (T,N,V,3), and ws as mh_mesh_bins filled it for THE SAME verts taken as
+ *   B = T N bodies; part (V) uint8, the part of every vertex; P <= 32 parts.  One lane per vertex,
+ *   which walks the other testable bodies m != n of its frame and drops a body whose box misses it
+ *   after reading that body's header.
+ *       mask[t][n][v]  uint32: bit m is set iff the vertex is INSIDE body m (N <= 32: one word);
+ *       depth[t][n][v] = the largest exit(q, m) over the bodies in the mask, in lattice units;
+ *       other[t][n][v] = the m that attains it, the smallest m on a tie; both -1 when the mask is 0;
+ *       pair_verts[t][n][m] = vertices of n inside m; pair_depth[t][n][m] = the largest exit over
+ *                        them, -1 if none (the diagonal is 0 / -1);
+ *       part_verts[t][n][k] = vertices with part[v] = k inside anybody; part_depth[t][n][k] = their
+ *                        largest depth, -1 if none.
+ *   The vertices of a person that is not live get 0 / -1 / -1 and count nowhere; a part[v] >= P counts
+ *   in no part.  Counts and maxima are accumulated in LDS per workgroup, then one integer atomic per
+ *   workgroup and accumulator, as mh_person_pairs does it; V need not be a multiple of the
+ *   workgroup.  Every output is overwritten by the call; each may be NULL, not all.
+ *   Refused before any HIP call: T, N, V or F <= 0; N > 32; P outside 1..32; T N V or 8 T N F beyond
+ *   one launch; NULL faces, ws, verts or part; every output NULL.
+ * The calls own nothing and keep nothing beyond the switch of mh_mesh_set_all_faces.                  */
+size_t mh_mesh_bins_bytes(int B, int F);
+int mh_mesh_bins(int B, int V, int F, const float* verts /*(B,V,3)*/, const int32_t* faces /*(F,3)*/,
+                 const uint8_t* live /*(B)*/, void* ws, size_t ws_bytes, int32_t* status /*(B)*/,
+                 void* stream);
+int mh_mesh_set_all_faces(int on);
+int mh_mesh_winding(int B, int V, int F, const int32_t* faces, const void* ws, int Q,
+                    const float* points /*(B,Q,3)*/, int32_t* winding /*(B,Q)*/, int32_t* up /*(B,Q)*/,
+                    int32_t* down /*(B,Q)*/, void* stream);
+int mh_person_inside(int T, int N, int V, int F, const int32_t* faces, const void* ws,
+                     const float* verts /*(T,N,V,3)*/, const uint8_t* part /*(V)*/, int P,
+                     uint32_t* mask /*(T,N,V)*/, int32_t* depth /*(T,N,V)*/, int32_t* other /*(T,N,V)*/,
+                     int32_t* pair_verts /*(T,N,N)*/, int32_t* pair_depth /*(T,N,N)*/,
+                     int32_t* part_verts /*(T,N,P)*/, int32_t* part_depth /*(T,N,P)*/, void* stream);
 
 /* ---- stand-alone forms of losses.py:19-40 and morphology.py:6-41 (call compatibility of
  * mhmocap.losses / mhmocap.morphology; the optimiser uses the fused kernels above) --------------

@@ -980,6 +980,47 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         out['frames'] = idx
         return out
 
+    # -- is one body inside another (the reference has a nearest-face-normal heuristic, unused) -------------------------------
+    def penetration_map(self, frames=None, chunk=8):
+        """Per vertex, which OTHER people of its frame the current leaves put it inside at ``frames`` (default: all), by the
+        exact winding-number test: dict of numpy arrays -- the columns of ``mhhip.inside.penetration_map``: ``inside``
+        (len(frames), N, V) bool, ``mask`` the containing bodies as bits, ``depth_z_m`` how far along the camera axis the vertex
+        is from leaving the body it is deepest in (inf outside), ``other`` that body, the per-pair tables ``pair_verts`` /
+        ``pair_depth_z_m`` (len(frames), N, N), the per-part tables ``part_verts`` / ``part_depth_z_m`` (len(frames), N, 24),
+        ``inside_verts`` and ``status`` (len(frames), N) -- plus ``'frames'``.  The vertices are those of ``predict``; a person
+        counts where the fit's thresholded ``valid_smpl`` says it is there; at most ``chunk`` frames are on the device at a time.
+        Needs no scene and no staged images.  Reads the leaves only: a workspace and buffers of its own, nothing of the
+        engine's state is written."""
+        from mhhip import inside as mhinside
+        if self.engine is None:
+            raise RuntimeError('penetration_map: nothing to measure before init_optimized_variables()')
+        if self._world()[0] > 1:
+            raise RuntimeError('penetration_map is not available in a frame-sharded run (world > 1): measure on the gathered '
+                               'result of get_optimized_variables() in one process')
+        e = self.engine
+        T, N = self.num_frames, self.num_people
+        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
+        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
+            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
+        idx = idx.astype(np.int64)
+        chunk = max(1, int(chunk))
+        m = self.SMPLPY.body_model
+        live = self._valid.reshape(T, N) > 0
+        parts = []
+        with torch.cuda.device(self.device), torch.no_grad():
+            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
+            for f0 in range(0, len(idx), chunk):
+                cur = torch.as_tensor(idx[f0:f0 + chunk], device=self.device)
+                nb = len(cur) * N
+                verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[cur].reshape(nb, 72), e.leaf('xscale').view(N),
+                                               pT_all[cur].reshape(nb, 3), want_vposed=False)
+                got = mhinside.penetration_map(m, verts.view(len(cur), N, -1, 3), live=live[idx[f0:f0 + chunk]], chunk=chunk)
+                parts.append({k: v.cpu().numpy() for k, v in got.items()})
+                del verts, got
+        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+        out['frames'] = idx
+        return out
+
     # -- reference optimizer.py:664-675 ---------------------------------------------------------------
     def one_euro_filter(self, x, min_cutoff=0.1, beta=0.02, frame_rate=25):
         x = torch.as_tensor(x).detach().to(self.device).float()
