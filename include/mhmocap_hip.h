@@ -1134,6 +1134,124 @@ int mh_person_inside(int T, int N, int V, int F, const int32_t* faces, const voi
                      int32_t* pair_verts /*(T,N,N)*/, int32_t* pair_depth /*(T,N,N)*/,
                      int32_t* part_verts /*(T,N,P)*/, int32_t* part_depth /*(T,N,P)*/, void* stream);
 
+/* ---- exact point-to-surface distance, and the person-to-person clearance map -------------------------
+ * How far is a point from the SURFACE of a triangle mesh, and which point of it is the nearest: for a
+ * vertex that mh_person_inside found inside another body the shortest way out, for every other vertex
+ * the clearance.  (mh_person_nearest measures to the nearest VERTEX, mh_person_inside's depth along z
+ * only.)  Read-only, off the cycle; no term of the fit.
+ *
+ * THE DEFINITION.  Everything is float32, evaluated in the order written, without contraction, so a
+ * float32 evaluation of the same expressions on the host gives the same bits (tests/surface_ref.py).
+ * With dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z, the squared distance D2 from the query q to the face
+ * (a, b, c) is the region method in its query-centred form:
+ *     A = a - q; B = b - q; C = c - q; ab = b - a; ac = c - a
+ *     d1 = -dot(ab, A); d2 = -dot(ac, A); d3 = -dot(ab, B); d4 = -dot(ac, B); d5 = -dot(ab, C);
+ *     d6 = -dot(ac, C)
+ *     vc = d1 d4 - d3 d2; vb = d5 d2 - d1 d6; va = d3 d6 - d5 d4; e1 = d4 - d3; e2 = d5 - d6
+ *     the first region that holds, in this order, gives (v, w):
+ *       d1 <= 0 && d2 <= 0               -> (0, 0)                          vertex a
+ *       d3 >= 0 && d4 <= d3              -> (1, 0)                          vertex b
+ *       vc <= 0 && d1 >= 0 && d3 <= 0    -> (d1 / (d1 - d3), 0)             edge ab
+ *       d6 >= 0 && d5 <= d6              -> (0, 1)                          vertex c
+ *       vb <= 0 && d2 >= 0 && d6 <= 0    -> (0, d2 / (d2 - d6))             edge ac
+ *       va <= 0 && e1 >= 0 && e2 >= 0    -> (1 - t, t), t = e1 / (e1 + e2)  edge bc
+ *       otherwise                        -> (vb / den, vc / den), den = (va + vb) + vc
+ *     x = (A + ab v) + ac w  (per component);  D2 = dot(x, x);
+ *     closest point = q + x;  weights = ((1 - v) - w, v, w).
+ *   The differences to the query are taken first, so near the surface they are exact and the result
+ *   does not lose digits with the distance from the origin.  Collinear and single-point faces give the
+ *   right distance through the edge and vertex regions.
+ * CANDIDATES of a query against a body: a face that names three vertices in [0, V) whose nine
+ *   coordinates are finite, whose D2 is not NaN, and D2 <= r2, r2 = radius radius (float32); a radius
+ *   of +inf admits every D2 that is not NaN.
+ * RESULT: the smallest candidate D2; on equal D2 the smallest face index (a query on a shared edge ties
+ *   between the two faces).  A function of the candidate SET, never of a visiting order or of the
+ *   search structure.  A query that is not finite, a dead body, and a query without a candidate give
+ *   D2 = +inf, face = -1 (and a point and weights of zeros).
+ *
+ * mh_surface_grid: B bodies verts (B,V,3) with the same faces (F,3); live (B) uint8 or NULL (all live).
+ *   Fills ws (at least mh_surface_grid_bytes(B, F) bytes) for mh_mesh_closest and mh_person_surface:
+ *   per body the box of its finite vertices, the three corners of every face (48 bytes, so a face visit
+ *   is three 16-byte loads), and a 3D uniform grid of face lists over the box: cubic cells, at most 64
+ *   per axis and at most min(max(F / 2, 256), 8192) in all, the smallest edge of the sequence
+ *   (longest extent) / 64 * 1.0625^i that satisfies both; a face is listed in every cell its bounding box
+ *   overlaps (count, scan, fill; integer atomics only).  The lists of a body hold at most 16 F entries;
+ *   a body that needs more -- a coarse mesh of a dozen huge faces -- or whose box overflows float32 is
+ *   marked and its queries walk all F faces.  The results are the same either way.
+ *   status[b] (may be NULL): bit 1 = not live, 4 = live and walking all faces.
+ *   mh_surface_set_all_faces(1) sends every live body of later mh_surface_grid calls down the
+ *   all-faces path (a yardstick for what the grid buys, and a test of the claim above); it returns the
+ *   previous setting, and 0 restores the default.
+ *   Refused before any HIP call: B, V or F <= 0; B V or 16 B F beyond one launch; NULL verts, faces or
+ *   ws; ws_bytes below mh_surface_grid_bytes.
+ * mh_mesh_closest: the generic query, points (B,Q,3): point j of row b against body b of the ws that
+ *   mh_surface_grid filled for the same B, V, F and faces.  One lane per point.  It drops the body when
+ *   its box, grown by the radius, misses the query, and otherwise walks the grid in rings of cells
+ *   around the cell of the query clamped into the box, nearest ring first, until a conservative lower
+ *   bound on the distance to every cell not yet visited exceeds the best D2; inside a ring a cell
+ *   whose own bound exceeds it is skipped (csrc/mh_surface.hip argues the bounds and their margin:
+ *   pruned only on strictly greater, so a tie with a smaller face index survives).  Every trip count is bounded by the grid's dimensions, never by
+ *   a distance: a query 1000 m away with radius = +inf costs one pass over the body's cells.
+ *   d2, face (B,Q), point, weights (B,Q,3): each may be NULL, not all.
+ *   Refused before any HIP call: B, V, F or Q <= 0; B Q or 16 B F beyond one launch; NULL faces, ws or
+ *   points; every output NULL; a radius that is NaN, <= 0 or -inf (+inf is allowed).
+ * mh_person_surface: verts (T,N,V,3), and ws as mh_surface_grid filled it for THE SAME verts taken as
+ *   B = T N bodies; mask (T,N,V) uint32 as mh_person_inside wrote it for them, or NULL (nobody is
+ *   inside anybody).  One lane per vertex v of a live person n with three finite coordinates, which
+ *   walks the other live bodies m != n of its frame:
+ *     bit m of the mask set: body m is searched with an UNBOUNDED radius and without the box test (the
+ *       vertex is in m's box, the walk ends after a few rings), so that every penetrating vertex gets
+ *       a depth, however deep it is;
+ *     otherwise: body m is searched with radius.
+ *       out_d2, out_idx = over the bodies that do NOT contain the vertex, the smallest D2 and
+ *                         m F + f of its face; on a tie the smallest m, then the smallest f;
+ *       in_d2, in_idx   = over the bodies that CONTAIN it, the LARGEST of its D2 to each body's
+ *                         surface (the body it is deepest in) and m F + f; on a tie the smallest m;
+ *       out_pt, in_pt (T,N,V,3) = the closest points themselves, zeros where there is none;
+ *       stats (T,N,V,2) int32 = bodies searched (not dropped at their box) and faces evaluated: what
+ *                         the measurements in DESIGN.md are made of.
+ *   Without a candidate (and for a dead person or a query that is not finite) D2 = +inf, idx = -1.
+ *   Every output is overwritten; each may be NULL, not all.
+ *   Refused before any HIP call: T, N, V or F <= 0; N > 32; N F >= 2^31; T N V or 16 T N F beyond one
+ *   launch; NULL faces, ws or verts; every output NULL; a radius that is NaN, <= 0 or -inf.
+ * mh_surface_pairs: out_d2, out_idx, in_d2, in_idx (T,N,V) as mh_person_surface wrote them; part (V)
+ *   uint8; P <= 32 parts; contact in metres, finite, >= 0; c2 = contact contact (float32).
+ *       pair_depth_d2[t][n][m] = the largest in_d2 over the vertices of n with in_idx / F = m,
+ *                                -1 when there is none;
+ *       pair_min_d2[t][n][m]   = the smallest out_d2 over the vertices of n with out_idx / F = m,
+ *                                +inf when there is none;
+ *       pair_contact[t][n][m]  = the number of those vertices with out_d2 <= c2;
+ *       part_depth_d2, part_min_d2, part_contact (T,N,P): the same three over the vertices with
+ *                                part[v] = k, whatever the other body.
+ *   A part[v] >= P counts in no part; an idx at or beyond N F is treated as idx < 0; a d2 that is NaN or
+ *   negative is never a minimum or a maximum.  Integer atomics only -- counts, and minima and maxima on
+ *   the BIT PATTERN of non-negative floats -- accumulated in LDS per workgroup, then one atomic per
+ *   workgroup and accumulator in device memory, as mh_person_pairs does it; V need not be a multiple
+ *   of the workgroup.  Every output is overwritten; each may be NULL, not all.
+ *   Refused before any HIP call: T, N, V or F <= 0; N > 32; P outside 1..32; N F >= 2^31; T N V beyond
+ *   one launch; NULL out_d2, out_idx, in_d2, in_idx or part; every output NULL; a contact that is not
+ *   finite or is negative.
+ * The calls own nothing and keep nothing beyond the switch of mh_surface_set_all_faces.               */
+size_t mh_surface_grid_bytes(int B, int F);
+int mh_surface_grid(int B, int V, int F, const float* verts /*(B,V,3)*/, const int32_t* faces /*(F,3)*/,
+                    const uint8_t* live /*(B)*/, void* ws, size_t ws_bytes, int32_t* status /*(B)*/,
+                    void* stream);
+int mh_surface_set_all_faces(int on);
+int mh_mesh_closest(int B, int V, int F, const int32_t* faces, const void* ws, int Q,
+                    const float* points /*(B,Q,3)*/, float radius, float* d2 /*(B,Q)*/,
+                    int32_t* face /*(B,Q)*/, float* point /*(B,Q,3)*/, float* weights /*(B,Q,3)*/,
+                    void* stream);
+int mh_person_surface(int T, int N, int V, int F, const int32_t* faces, const void* ws,
+                      const float* verts /*(T,N,V,3)*/, const uint32_t* mask /*(T,N,V)*/, float radius,
+                      float* out_d2, int32_t* out_idx, float* in_d2, int32_t* in_idx /*(T,N,V)*/,
+                      float* out_pt, float* in_pt /*(T,N,V,3)*/, int32_t* stats /*(T,N,V,2)*/,
+                      void* stream);
+int mh_surface_pairs(int T, int N, int V, int F, const float* out_d2, const int32_t* out_idx,
+                     const float* in_d2, const int32_t* in_idx, const uint8_t* part /*(V)*/, int P,
+                     float contact, float* pair_depth_d2 /*(T,N,N)*/, float* pair_min_d2 /*(T,N,N)*/,
+                     int32_t* pair_contact /*(T,N,N)*/, float* part_depth_d2 /*(T,N,P)*/,
+                     float* part_min_d2 /*(T,N,P)*/, int32_t* part_contact /*(T,N,P)*/, void* stream);
+
 /* ---- stand-alone forms of losses.py:19-40 and morphology.py:6-41 (call compatibility of
  * mhmocap.losses / mhmocap.morphology; the optimiser uses the fused kernels above) --------------
  * mh_avg_depth_loss: rows = b*N maps of P pixels; `tru` has rows/group maps (group = N when the

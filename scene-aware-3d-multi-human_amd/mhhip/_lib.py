@@ -202,6 +202,13 @@ def lib():
         L.mh_mesh_set_all_faces.argtypes = [ctypes.c_int]
         L.mh_mesh_winding.argtypes = [ctypes.c_int] * 3 + [vp, vp, ctypes.c_int] + [vp] * 5
         L.mh_person_inside.argtypes = [ctypes.c_int] * 4 + [vp] * 4 + [ctypes.c_int] + [vp] * 8
+        L.mh_surface_grid_bytes.restype = ctypes.c_size_t
+        L.mh_surface_grid_bytes.argtypes = [ctypes.c_int] * 2
+        L.mh_surface_grid.argtypes = [ctypes.c_int] * 3 + [vp] * 4 + [ctypes.c_size_t, vp, vp]
+        L.mh_surface_set_all_faces.argtypes = [ctypes.c_int]
+        L.mh_mesh_closest.argtypes = [ctypes.c_int] * 3 + [vp, vp, ctypes.c_int, vp, ctypes.c_float] + [vp] * 5
+        L.mh_person_surface.argtypes = [ctypes.c_int] * 4 + [vp] * 4 + [ctypes.c_float] + [vp] * 8
+        L.mh_surface_pairs.argtypes = [ctypes.c_int] * 4 + [vp] * 5 + [ctypes.c_int, ctypes.c_float] + [vp] * 7
         L.mh_view_project.argtypes = [ctypes.c_int] * 3 + [vp, c_float_p, c_float_p, c_float_p, ctypes.c_float, vp, vp]
         L.mh_view_clear.argtypes = [ctypes.c_int] * 3 + [vp, vp]
         L.mh_view_raster.argtypes = [ctypes.c_int] * 6 + [vp] * 4

@@ -1021,6 +1021,51 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         out['frames'] = idx
         return out
 
+    # -- how deep along the shortest way out, and how much room between bodies that do not overlap -------------------------------
+    def clearance_map(self, frames=None, radius=0.1, contact=0.02, nearest=False, chunk=8):
+        """Per vertex, the signed distance the current leaves put between it and the SURFACE of the other people of its frame
+        at ``frames`` (default: all): dict of numpy arrays -- the columns of ``mhhip.surface.clearance_map``: ``signed_m``
+        (len(frames), N, V) minus the distance to the surface of the body the vertex is deepest in where the exact inside
+        test says it is inside one, else ``dist_m``, the distance to the nearest surface within ``radius`` (inf beyond it);
+        ``depth_m``; ``other`` and ``face`` that decide ``signed_m``; ``inside`` and ``mask`` as ``penetration_map`` gives them;
+        the per-pair tables ``pair_depth_m`` / ``pair_min_dist_m`` / ``pair_contact_verts`` (len(frames), N, N), the per-part
+        tables ``part_depth_m`` / ``part_min_dist_m`` / ``part_contact_verts`` (len(frames), N, 24), ``status``
+        (len(frames), N), with ``nearest=True`` also ``point`` (len(frames), N, V, 3), the closest surface point: the way out
+        or the way to contact -- plus ``'frames'``.  The vertices are those of ``predict``; a person counts where the fit's
+        thresholded ``valid_smpl`` says it is there; at most ``chunk`` frames are on the device at a time.  Needs no scene and
+        no staged images.  Reads the leaves only: workspaces and buffers of its own, nothing of the engine's state is
+        written."""
+        from mhhip import surface as mhsurface
+        if self.engine is None:
+            raise RuntimeError('clearance_map: nothing to measure before init_optimized_variables()')
+        if self._world()[0] > 1:
+            raise RuntimeError('clearance_map is not available in a frame-sharded run (world > 1): measure on the gathered '
+                               'result of get_optimized_variables() in one process')
+        e = self.engine
+        T, N = self.num_frames, self.num_people
+        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
+        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
+            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
+        idx = idx.astype(np.int64)
+        chunk = max(1, int(chunk))
+        m = self.SMPLPY.body_model
+        live = self._valid.reshape(T, N) > 0
+        parts = []
+        with torch.cuda.device(self.device), torch.no_grad():
+            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
+            for f0 in range(0, len(idx), chunk):
+                cur = torch.as_tensor(idx[f0:f0 + chunk], device=self.device)
+                nb = len(cur) * N
+                verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[cur].reshape(nb, 72), e.leaf('xscale').view(N),
+                                               pT_all[cur].reshape(nb, 3), want_vposed=False)
+                got = mhsurface.clearance_map(m, verts.view(len(cur), N, -1, 3), live=live[idx[f0:f0 + chunk]], radius=radius,
+                                              contact=contact, nearest=nearest, chunk=chunk)
+                parts.append({k: v.cpu().numpy() for k, v in got.items()})
+                del verts, got
+        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+        out['frames'] = idx
+        return out
+
     # -- reference optimizer.py:664-675 ---------------------------------------------------------------
     def one_euro_filter(self, x, min_cutoff=0.1, beta=0.02, frame_rate=25):
         x = torch.as_tensor(x).detach().to(self.device).float()
