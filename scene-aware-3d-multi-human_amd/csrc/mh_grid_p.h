@@ -1,7 +1,9 @@
 // The uniform grid over the scene cloud: the header the build writes on the device, the layout of the caller's workspace
 // (mh_scene_grid_bytes) and the cell of a point.  Internal to the library (not part of the C ABI); included by
-// mh_scene.hip, which builds the grid and searches it for the contact term, and by mh_contact.hip.
+// mh_scene.hip, which builds the grid and searches it for the contact term, and by mh_contact.hip.  The build's shared parts
+// (workspace layout, box reduction, scan) are those of mh_cells_p.h.
 #pragma once
+#include "mh_cells_p.h"
 #include "mh_common.h"
 
 #define GRID_MAX_CELLS (1 << 20)
@@ -21,7 +23,6 @@ __device__ __forceinline__ int grid_cell(const GridHdr* h, float x, float y, flo
   return (cz * h->dim[1] + cy) * h->dim[0] + cx;
 }
 
-static size_t g_align(size_t x) { return (x + 255) & ~(size_t)255; }
 struct GridWs {
   GridHdr* hdr;
   int* start;     // [GRID_MAX_CELLS + 1]
@@ -29,13 +30,8 @@ struct GridWs {
   int* pcell;     // [M]
   float* sorted;  // [M][3]
 };
-static GridWs grid_carve(void* ws, int M) {
-  char* c = (char*)ws;
-  GridWs g;
-  g.hdr = (GridHdr*)c; c += g_align(sizeof(GridHdr));
-  g.start = (int*)c; c += g_align((size_t)(GRID_MAX_CELLS + 1) * 4);
-  g.cursor = (int*)c; c += g_align((size_t)GRID_MAX_CELLS * 4);
-  g.pcell = (int*)c; c += g_align((size_t)M * 4);
-  g.sorted = (float*)c;
-  return g;
+static size_t grid_bytes(size_t M) { return cells_bytes(1, sizeof(GridHdr), GRID_MAX_CELLS, M * 4, M * 12); }
+static GridWs grid_carve(void* ws, int M) {     // the layout of mh_cells_p.h for one body
+  const CellsWs c = cells_carve(ws, 1, sizeof(GridHdr), GRID_MAX_CELLS, (size_t)M * 4);
+  return {(GridHdr*)c.hdr, c.start, c.cursor, (int*)c.a, (float*)c.b};
 }

@@ -22,6 +22,7 @@
 // fits an int32; an edge function is a difference of two products of such differences, |E| <= 2^39; A = w0 + w1 + w2 is
 // twice the signed area of the projected face, |A| <= 2^38; Nn is three products of a w and a z difference,
 // |Nn| <= 3 2^58 < 2^61; on a covering face the w have one sign, so |Nn| <= |A| 2^19 and dz = |Nn| / |A| <= 2^19.
+#include "mh_cells_p.h"
 #include "mh_common.h"
 
 #include <limits.h>
@@ -52,27 +53,17 @@ struct MiHdr {                      // device-resident, one per body (written by
   unsigned long long total;         // entries the cell lists would need
 };
 
-static size_t mi_align(size_t x) { return (x + 255) & ~(size_t)255; }
-struct MiWs {
+struct MiWs {                       // the layout of mh_cells_p.h
   MiHdr* hdr;                       // [B]
   int* start;                       // [B][MI_MAX_CELLS + 1]
   int* cursor;                      // [B][MI_MAX_CELLS]
   int4* rec;                        // [B][F][3]   (X, Y, Z, valid) of the three corners; valid in the first only
   int* list;                        // [B][MI_CAP_PER_FACE F]   faces by cell
 };
-static size_t mi_bytes(size_t B, size_t F) {
-  return mi_align(B * sizeof(MiHdr)) + mi_align(B * (MI_MAX_CELLS + 1) * 4) + mi_align(B * MI_MAX_CELLS * 4) + mi_align(B * F * 48) +
-         mi_align(B * F * MI_CAP_PER_FACE * 4);
-}
+static size_t mi_bytes(size_t B, size_t F) { return cells_bytes(B, sizeof(MiHdr), MI_MAX_CELLS, B * F * 48, B * F * MI_CAP_PER_FACE * 4); }
 static MiWs mi_carve(void* ws, size_t B, size_t F) {
-  char* c = (char*)ws;
-  MiWs w;
-  w.hdr = (MiHdr*)c; c += mi_align(B * sizeof(MiHdr));
-  w.start = (int*)c; c += mi_align(B * (MI_MAX_CELLS + 1) * 4);
-  w.cursor = (int*)c; c += mi_align(B * MI_MAX_CELLS * 4);
-  w.rec = (int4*)c; c += mi_align(B * F * 48);
-  w.list = (int*)c;
-  return w;
+  const CellsWs c = cells_carve(ws, B, sizeof(MiHdr), MI_MAX_CELLS, B * F * 48);
+  return {(MiHdr*)c.hdr, c.start, c.cursor, (int4*)c.a, (int*)c.b};
 }
 
 __device__ __forceinline__ bool mi_finite(float x) { return fabsf(x) < INFINITY; }            // (false for NaN)
@@ -83,7 +74,6 @@ __device__ __forceinline__ int mi_lattice(float x) { return (int)rintf(x * MI_SC
 // ---- build: boxes, face records and totals, counts, scan, fill ----------------------------------------------------------------
 // one workgroup per body: is it testable, the lattice box of its finite vertices, the grid's shape, and the cleared counts
 __global__ __launch_bounds__(MI_BLOCK) void k_mi_setup(int V, int F, const float* verts, const uint8_t* live, MiHdr* hdrs, int* start) {
-  __shared__ int smn[3][MI_BLOCK / 64], smx[3][MI_BLOCK / 64];
   __shared__ int scnt[MI_BLOCK / 64], sbad[MI_BLOCK / 64];
   __shared__ int s_nc;
   const size_t b = blockIdx.x;
@@ -111,22 +101,11 @@ __global__ __launch_bounds__(MI_BLOCK) void k_mi_setup(int V, int F, const float
   for (int o = 32; o > 0; o >>= 1) {
     cnt += __shfl_xor(cnt, o, 64);
     bad |= __shfl_xor(bad, o, 64);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      mn[c] = min(mn[c], __shfl_xor(mn[c], o, 64));
-      mx[c] = max(mx[c], __shfl_xor(mx[c], o, 64));
-    }
   }
-  if ((tid & 63) == 0) {
-    scnt[tid >> 6] = cnt; sbad[tid >> 6] = bad;
-    for (int c = 0; c < 3; ++c) { smn[c][tid >> 6] = mn[c]; smx[c][tid >> 6] = mx[c]; }
-  }
-  __syncthreads();
+  if ((tid & 63) == 0) { scnt[tid >> 6] = cnt; sbad[tid >> 6] = bad; }
+  cells_box_reduce<MI_BLOCK>(mn, mx);                       // (its barrier publishes scnt and sbad too)
   if (tid == 0) {
-    for (int w = 1; w < MI_BLOCK / 64; ++w) {
-      cnt += scnt[w]; bad |= sbad[w];
-      for (int c = 0; c < 3; ++c) { mn[c] = min(mn[c], smn[c][w]); mx[c] = max(mx[c], smx[c][w]); }
-    }
+    for (int w = 1; w < MI_BLOCK / 64; ++w) { cnt += scnt[w]; bad |= sbad[w]; }
     MiHdr h;
     int flags = alive ? 0 : MI_NOT_LIVE;
     if (alive && (cnt == 0 || bad)) flags |= MI_NOT_TESTABLE;
@@ -155,22 +134,35 @@ __global__ __launch_bounds__(MI_BLOCK) void k_mi_setup(int V, int F, const float
   for (int i = tid; i <= nc; i += MI_BLOCK) counts[i] = 0;
 }
 
-// the cells [x0, x1] x [y0, y1] that the closed xy box of a face record overlaps
-__device__ __forceinline__ void mi_face_cells(const MiHdr& h, const int4 a, const int4 b, const int4 c, int& x0, int& x1, int& y0, int& y1) {
-  x0 = (min(a.x, min(b.x, c.x)) - h.mn[0]) >> h.shift;
-  x1 = (max(a.x, max(b.x, c.x)) - h.mn[0]) >> h.shift;
-  y0 = (min(a.y, min(b.y, c.y)) - h.mn[1]) >> h.shift;
-  y1 = (max(a.y, max(b.y, c.y)) - h.mn[1]) >> h.shift;
-  x0 = max(x0, 0); y0 = max(y0, 0);                        // (a finite vertex of a testable body is inside its box: never clips)
-  x1 = min(x1, h.dx - 1); y1 = min(y1, h.dy - 1);
-}
+__device__ __forceinline__ bool mi_walks_all(const MiHdr& h, int F, int force) { return force != 0 || cells_over_cap(h.total, F, MI_CAP_PER_FACE); }
+
+struct MiGrid {                     // the face grid of mh_cells_p.h: two-dimensional, over x and y of the lattice
+  typedef MiHdr Hdr;
+  typedef int4 Rec;
+  static constexpr int BLOCK = MI_BLOCK, MAX_CELLS = MI_MAX_CELLS, CAP_PER_FACE = MI_CAP_PER_FACE;
+  static __device__ __forceinline__ bool counted(const MiHdr& h, int F, int force) {
+    return !(h.flags & (MI_NOT_LIVE | MI_NOT_TESTABLE)) && !mi_walks_all(h, F, force);
+  }
+  static __device__ __forceinline__ bool valid(const int4& r) { return r.w != 0; }
+  // the cells [c0, c1] of x and y that the closed xy box of a face record overlaps (one layer: z is not binned)
+  static __device__ __forceinline__ void range(const MiHdr& h, const int4 a, const int4 b, const int4 c, int c0[3], int c1[3]) {
+    c0[0] = (min(a.x, min(b.x, c.x)) - h.mn[0]) >> h.shift;
+    c1[0] = (max(a.x, max(b.x, c.x)) - h.mn[0]) >> h.shift;
+    c0[1] = (min(a.y, min(b.y, c.y)) - h.mn[1]) >> h.shift;
+    c1[1] = (max(a.y, max(b.y, c.y)) - h.mn[1]) >> h.shift;
+    c0[0] = max(c0[0], 0); c0[1] = max(c0[1], 0);          // (a finite vertex of a testable body is inside its box: never clips)
+    c1[0] = min(c1[0], h.dx - 1); c1[1] = min(c1[1], h.dy - 1);
+    c0[2] = c1[2] = 0;
+  }
+  static __device__ __forceinline__ int cell(const MiHdr& h, int cx, int cy, int) { return cy * h.dx + cx; }
+};
 
 // one lane per (body, face), the workgroups of a body consecutive: the face's lattice record, and the entries it would need
 __global__ __launch_bounds__(MI_BLOCK) void k_mi_faces(int V, int F, int fpb, const float* verts, const int* faces, MiHdr* hdrs, int4* rec) {
   __shared__ int s_total;
   const int tid = threadIdx.x;
-  const size_t b = blockIdx.x / fpb;
-  const int f = (int)(blockIdx.x - b * fpb) * MI_BLOCK + tid;
+  size_t b;
+  const int f = cells_body_face<MI_BLOCK>(fpb, b);
   if (tid == 0) s_total = 0;
   __syncthreads();
   const MiHdr h = hdrs[b];
@@ -194,40 +186,19 @@ __global__ __launch_bounds__(MI_BLOCK) void k_mi_faces(int V, int F, int fpb, co
     int4* o = rec + (b * F + f) * 3;
     o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
     if (ok) {
-      int x0, x1, y0, y1;
-      mi_face_cells(h, r[0], r[1], r[2], x0, x1, y0, y1);
-      atomicAdd(&s_total, (x1 - x0 + 1) * (y1 - y0 + 1));                      // (<= 256 x 4096: no overflow)
+      int c0[3], c1[3];
+      MiGrid::range(h, r[0], r[1], r[2], c0, c1);
+      atomicAdd(&s_total, (c1[0] - c0[0] + 1) * (c1[1] - c0[1] + 1));          // (<= 256 x 4096: no overflow)
     }
   }
   __syncthreads();
   if (tid == 0 && s_total != 0) atomicAdd(&hdrs[b].total, (unsigned long long)s_total);
 }
 
-__device__ __forceinline__ bool mi_walks_all(const MiHdr& h, int F, int force) {
-  return force != 0 || h.total > (unsigned long long)MI_CAP_PER_FACE * (unsigned long long)F;
-}
-
-// one lane per (body, face): the face counted in every cell of its box (grid-path bodies only: at most 8 F atomics a body)
-__global__ __launch_bounds__(MI_BLOCK) void k_mi_count(int F, int fpb, int force, const MiHdr* hdrs, const int4* rec, int* start) {
-  const size_t b = blockIdx.x / fpb;
-  const int f = (int)(blockIdx.x - b * fpb) * MI_BLOCK + threadIdx.x;
-  if (f >= F) return;
-  const MiHdr h = hdrs[b];
-  if ((h.flags & (MI_NOT_LIVE | MI_NOT_TESTABLE)) || mi_walks_all(h, F, force)) return;
-  const int4* r = rec + (b * F + f) * 3;
-  const int4 p0 = r[0], p1 = r[1], p2 = r[2];
-  if (!p0.w) return;
-  int x0, x1, y0, y1;
-  mi_face_cells(h, p0, p1, p2, x0, x1, y0, y1);
-  int* counts = start + b * (MI_MAX_CELLS + 1);
-  for (int cy = y0; cy <= y1; ++cy)
-    for (int cx = x0; cx <= x1; ++cx) atomicAdd(&counts[cy * h.dx + cx], 1);
-}
+// (the counts and the fill are k_cells_count<MiGrid> and k_cells_fill<MiGrid>: at most 8 F atomics a body)
 
 // one workgroup per body: the path it takes and its status word; exclusive scan of its counts in place, and the fill cursors
 __global__ __launch_bounds__(1024) void k_mi_scan(int F, int force, MiHdr* hdrs, int* start, int* cursor, int* status) {
-  __shared__ int swave[16];
-  __shared__ int carry;
   const size_t b = blockIdx.x;
   const MiHdr h = hdrs[b];
   const bool testable = (h.flags & (MI_NOT_LIVE | MI_NOT_TESTABLE)) == 0;
@@ -236,52 +207,9 @@ __global__ __launch_bounds__(1024) void k_mi_scan(int F, int force, MiHdr* hdrs,
     const int flags = h.flags | (all ? MI_ALL_FACES : 0);
     hdrs[b].flags = flags;
     if (status) status[b] = flags;
-    carry = 0;
   }
   if (!testable || all) return;                            // (uniform over the workgroup)
-  int* counts = start + b * (MI_MAX_CELLS + 1);
-  int* cur = cursor + b * MI_MAX_CELLS;
-  const int nc = min(h.dx * h.dy, MI_MAX_CELLS), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  for (int base = 0; base < nc; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = i < nc ? counts[i] : 0;
-    const int incl = mh_wave_scan_add(v);
-    if (lane == 63) swave[wave] = incl;
-    __syncthreads();
-    int woff = carry;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) woff += (w < wave) ? swave[w] : 0;
-    if (i < nc) {
-      counts[i] = woff + incl - v;
-      cur[i] = woff + incl - v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = woff + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[nc] = carry;
-}
-
-__global__ __launch_bounds__(MI_BLOCK) void k_mi_fill(int F, int fpb, const MiHdr* hdrs, const int4* rec, int* cursor, int* list) {
-  const size_t b = blockIdx.x / fpb;
-  const int f = (int)(blockIdx.x - b * fpb) * MI_BLOCK + threadIdx.x;
-  if (f >= F) return;
-  const MiHdr h = hdrs[b];
-  if (h.flags != 0) return;                                // dead, not testable, or walking all faces
-  const int4* r = rec + (b * F + f) * 3;
-  const int4 p0 = r[0], p1 = r[1], p2 = r[2];
-  if (!p0.w) return;
-  int x0, x1, y0, y1;
-  mi_face_cells(h, p0, p1, p2, x0, x1, y0, y1);
-  int* cur = cursor + b * MI_MAX_CELLS;
-  int* lst = list + b * (size_t)F * MI_CAP_PER_FACE;
-  const long long cap = (long long)F * MI_CAP_PER_FACE;
-  for (int cy = y0; cy <= y1; ++cy)
-    for (int cx = x0; cx <= x1; ++cx) {
-      const int pos = atomicAdd(&cur[cy * h.dx + cx], 1);
-      if (pos >= 0 && pos < cap) lst[pos] = f;             // (cannot miss after the count; a lane never leaves its body's slab)
-    }
+  cells_scan_1024(min(h.dx * h.dy, MI_MAX_CELLS), start + b * (MI_MAX_CELLS + 1), cursor + b * MI_MAX_CELLS);
 }
 
 // ---- the test of one face ---------------------------------------------------------------------------------------------------------
@@ -329,13 +257,7 @@ __device__ __forceinline__ bool mi_query(const MiHdr& h, int F, const int4* __re
     for (int f = 0; f < F; ++f) mi_face(rec + (size_t)f * 3, qx, qy, qz, acc);
   } else {
     const int c = ((qy - h.mn[1]) >> h.shift) * h.dx + ((qx - h.mn[0]) >> h.shift);
-    const long long cap = (long long)F * MI_CAP_PER_FACE;
-    const int a = max(start[c], 0);
-    const int e = (int)min((long long)start[c + 1], cap);
-    for (int k = a; k < e; ++k) {
-      const int f = list[k];
-      if ((unsigned)f < (unsigned)F) mi_face(rec + (size_t)f * 3, qx, qy, qz, acc);
-    }
+    cells_visit(start, list, c, F, MI_CAP_PER_FACE, [&](int f) { mi_face(rec + (size_t)f * 3, qx, qy, qz, acc); });
   }
   return true;
 }
@@ -469,11 +391,11 @@ extern "C" int mh_mesh_bins(int B, int V, int F, const float* verts, const int32
   MH_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_mi_faces, dim3(nblk), dim3(MI_BLOCK), 0, st, V, F, fpb, verts, faces, w.hdr, w.rec);
   MH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_mi_count, dim3(nblk), dim3(MI_BLOCK), 0, st, F, fpb, force, (const MiHdr*)w.hdr, (const int4*)w.rec, w.start);
+  hipLaunchKernelGGL(k_cells_count<MiGrid>, dim3(nblk), dim3(MI_BLOCK), 0, st, F, fpb, force, (const MiHdr*)w.hdr, (const int4*)w.rec, w.start);
   MH_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_mi_scan, dim3((unsigned)B), dim3(1024), 0, st, F, force, w.hdr, w.start, w.cursor, status);
   MH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_mi_fill, dim3(nblk), dim3(MI_BLOCK), 0, st, F, fpb, (const MiHdr*)w.hdr, (const int4*)w.rec, w.cursor, w.list);
+  hipLaunchKernelGGL(k_cells_fill<MiGrid>, dim3(nblk), dim3(MI_BLOCK), 0, st, F, fpb, (const MiHdr*)w.hdr, (const int4*)w.rec, w.cursor, w.list);
   MH_LAUNCH_CHECK();
   return MH_OK;
 }

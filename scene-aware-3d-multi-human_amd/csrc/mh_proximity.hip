@@ -14,6 +14,7 @@
 //
 // The arithmetic is written in the order the header states and compiled without contraction: a float32 evaluation of the
 // same expressions on the host gives the same bits (tests/proximity_ref.py).
+#include "mh_cells_p.h"
 #include "mh_common.h"
 
 #include <float.h>
@@ -37,27 +38,17 @@ struct PnHdr {          // device-resident, one per body (written by k_pn_setup)
   int npts;             // finite vertices of a live body; 0: nothing to find here
 };
 
-static size_t pn_align(size_t x) { return (x + 255) & ~(size_t)255; }
-struct PnWs {
+struct PnWs {         // the layout of mh_cells_p.h
   PnHdr* hdr;        // [B]
   int* start;        // [B][PN_MAX_CELLS + 1]
   int* cursor;       // [B][PN_MAX_CELLS]
   int* pcell;        // [B][V]   cell of every vertex, -1: not binned
   uint4* sorted;     // [B][V]   (x, y, z bits, vertex index) by cell
 };
-static size_t pn_bytes(size_t B, size_t V) {
-  return pn_align(B * sizeof(PnHdr)) + pn_align(B * (PN_MAX_CELLS + 1) * 4) + pn_align(B * PN_MAX_CELLS * 4) + pn_align(B * V * 4) +
-         pn_align(B * V * 16);
-}
+static size_t pn_bytes(size_t B, size_t V) { return cells_bytes(B, sizeof(PnHdr), PN_MAX_CELLS, B * V * 4, B * V * 16); }
 static PnWs pn_carve(void* ws, size_t B, size_t V) {
-  char* c = (char*)ws;
-  PnWs w;
-  w.hdr = (PnHdr*)c; c += pn_align(B * sizeof(PnHdr));
-  w.start = (int*)c; c += pn_align(B * (PN_MAX_CELLS + 1) * 4);
-  w.cursor = (int*)c; c += pn_align(B * PN_MAX_CELLS * 4);
-  w.pcell = (int*)c; c += pn_align(B * V * 4);
-  w.sorted = (uint4*)c;
-  return w;
+  const CellsWs c = cells_carve(ws, B, sizeof(PnHdr), PN_MAX_CELLS, B * V * 4);
+  return {(PnHdr*)c.hdr, c.start, c.cursor, (int*)c.a, (uint4*)c.b};
 }
 
 __device__ __forceinline__ bool pn_finite3(float x, float y, float z) {
@@ -92,7 +83,6 @@ __device__ __forceinline__ bool pn_axis(float q, float rp, float mn, float mx, f
 // ---- build: boxes, counts, scan, scatter -------------------------------------------------------------------------------------
 // one workgroup per body: the box of its finite vertices, the grid's shape, and the cleared counts
 __global__ __launch_bounds__(PN_BLOCK) void k_pn_setup(int V, const float* verts, const uint8_t* live, PnHdr* hdrs, int* start) {
-  __shared__ float smn[3][PN_BLOCK / 64], smx[3][PN_BLOCK / 64];
   __shared__ int scnt[PN_BLOCK / 64];
   __shared__ int s_nc;
   const size_t b = blockIdx.x;
@@ -109,24 +99,11 @@ __global__ __launch_bounds__(PN_BLOCK) void k_pn_setup(int V, const float* verts
       for (int c = 0; c < 3; ++c) { mn[c] = fminf(mn[c], p[c]); mx[c] = fmaxf(mx[c], p[c]); }
     }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o, 64);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      mn[c] = fminf(mn[c], __shfl_xor(mn[c], o, 64));
-      mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], o, 64));
-    }
-  }
-  if ((tid & 63) == 0) {
-    scnt[tid >> 6] = cnt;
-    for (int c = 0; c < 3; ++c) { smn[c][tid >> 6] = mn[c]; smx[c][tid >> 6] = mx[c]; }
-  }
-  __syncthreads();
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if ((tid & 63) == 0) scnt[tid >> 6] = cnt;
+  cells_box_reduce<PN_BLOCK>(mn, mx);                       // (its barrier publishes scnt too)
   if (tid == 0) {
-    for (int w = 1; w < PN_BLOCK / 64; ++w) {
-      cnt += scnt[w];
-      for (int c = 0; c < 3; ++c) { mn[c] = fminf(mn[c], smn[c][w]); mx[c] = fmaxf(mx[c], smx[c][w]); }
-    }
+    for (int w = 1; w < PN_BLOCK / 64; ++w) cnt += scnt[w];
     PnHdr h;
     h.npts = cnt;
     float ext[3];
@@ -184,34 +161,10 @@ __global__ __launch_bounds__(PN_BLOCK) void k_pn_count(int total, int V, const f
   pcell[i] = c;
 }
 
-// one workgroup per body: exclusive scan of its counts[0..ncells] in place, and the fill cursors (k_grid_scan's form)
+// one workgroup per body: exclusive scan of its counts[0..ncells] in place, and the fill cursors
 __global__ __launch_bounds__(1024) void k_pn_scan(const PnHdr* hdrs, int* start, int* cursor) {
-  __shared__ int swave[16];
-  __shared__ int carry;
   const size_t b = blockIdx.x;
-  int* counts = start + b * (PN_MAX_CELLS + 1);
-  int* cur = cursor + b * PN_MAX_CELLS;
-  const int nc = min(hdrs[b].ncells, PN_MAX_CELLS), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nc; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = i < nc ? counts[i] : 0;
-    const int incl = mh_wave_scan_add(v);
-    if (lane == 63) swave[wave] = incl;
-    __syncthreads();
-    int woff = carry;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) woff += (w < wave) ? swave[w] : 0;
-    if (i < nc) {
-      counts[i] = woff + incl - v;
-      cur[i] = woff + incl - v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = woff + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[nc] = carry;
+  cells_scan_1024(min(hdrs[b].ncells, PN_MAX_CELLS), start + b * (PN_MAX_CELLS + 1), cursor + b * PN_MAX_CELLS);
 }
 
 __global__ __launch_bounds__(PN_BLOCK) void k_pn_scatter(int total, int V, const float* verts, const int* pcell, int* cursor, uint4* sorted) {

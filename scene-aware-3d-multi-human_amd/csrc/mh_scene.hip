@@ -419,7 +419,6 @@ extern "C" int mh_scene_unproject(const float* depth, int H, int W, const float*
 // evaluations for M = 2e4..2e5.
 // =============================================================================================
 __global__ __launch_bounds__(1024) void k_grid_setup(const float* pts, int M_host, const int* M_dev, GridHdr* hdr, int* counts, int max_cells) {
-  __shared__ float smn[3][16], smx[3][16];
   const int M = M_dev ? *M_dev : M_host;
   float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int i = threadIdx.x; i < M; i += 1024)
@@ -429,22 +428,10 @@ __global__ __launch_bounds__(1024) void k_grid_setup(const float* pts, int M_hos
       mn[c] = fminf(mn[c], v);
       mx[c] = fmaxf(mx[c], v);
     }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mn[c] = fminf(mn[c], __shfl_xor(mn[c], o, 64));
-      mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], o, 64));
-    }
-    if ((threadIdx.x & 63) == 0) { smn[c][threadIdx.x >> 6] = mn[c]; smx[c][threadIdx.x >> 6] = mx[c]; }
-  }
-  __syncthreads();
+  cells_box_reduce<1024>(mn, mx);
   if (threadIdx.x == 0) {
     float ext[3];
-    for (int c = 0; c < 3; ++c) {
-      for (int w = 1; w < 16; ++w) { mn[c] = fminf(mn[c], smn[c][w]); mx[c] = fmaxf(mx[c], smx[c][w]); }
-      ext[c] = fmaxf(mx[c] - mn[c], 1e-3f);
-    }
+    for (int c = 0; c < 3; ++c) ext[c] = fmaxf(mx[c] - mn[c], 1e-3f);
     // the clouds are surfaces: aim at ~16 points per occupied cell of the largest face of the bbox
     const float area = fmaxf(ext[0] * ext[1], fmaxf(ext[1] * ext[2], ext[0] * ext[2]));
     float cell = fminf(fmaxf(sqrtf(area * 16.f / (float)max(M, 1)), 0.02f), 4.f);
@@ -474,33 +461,9 @@ __global__ void k_grid_count(const float* pts, const GridHdr* hdr, int* counts, 
   atomicAdd(&counts[c], 1);
 }
 
-// exclusive scan of counts[0..ncells] in place (single block), also resets the fill cursors: DPP scan inside the
-// waves, one LDS hop for the 16 wave totals
+// exclusive scan of counts[0..ncells] in place (single block), also resets the fill cursors
 __global__ __launch_bounds__(1024) void k_grid_scan(const GridHdr* hdr, int* counts, int* cursor) {
-  __shared__ int swave[16];
-  __shared__ int carry;
-  const int nc = hdr->ncells, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nc; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = i < nc ? counts[i] : 0;
-    const int incl = mh_wave_scan_add(v);
-    if (lane == 63) swave[wave] = incl;
-    __syncthreads();
-    int woff = carry;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) woff += (w < wave) ? swave[w] : 0;
-    if (i < nc) {
-      const int start = woff + incl - v;
-      counts[i] = start;
-      cursor[i] = start;
-    }
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = woff + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[nc] = carry;
+  cells_scan_1024(hdr->ncells, counts, cursor);
 }
 
 __global__ void k_grid_scatter(const float* pts, const GridHdr* hdr, const int* pcell, int* cursor, float* sorted) {
@@ -513,8 +476,7 @@ __global__ void k_grid_scatter(const float* pts, const GridHdr* hdr, const int* 
 }
 
 extern "C" size_t mh_scene_grid_bytes(int M) {
-  return g_align(sizeof(GridHdr)) + g_align((size_t)(GRID_MAX_CELLS + 1) * 4) + g_align((size_t)GRID_MAX_CELLS * 4) +
-         g_align((size_t)(M > 0 ? M : 1) * 4) + g_align((size_t)(M > 0 ? M : 1) * 12);
+  return grid_bytes((size_t)(M > 0 ? M : 1));
 }
 
 static int grid_build(const float* points, int M, const int* M_dev, void* grid_ws, hipStream_t st) {

@@ -48,6 +48,7 @@
 // candidate or tie the best; a face skipped there is met through c* or is none.  Without this a ring of 26 cells was walked
 // whole although the best face so far was nearer than most of them.
 // The test of the claim is tests/test_surface_gpu.py: the grid path and the forced all-faces path must agree bit for bit.
+#include "mh_cells_p.h"
 #include "mh_common.h"
 
 #include <float.h>
@@ -83,27 +84,17 @@ struct MsHdr {                      // device-resident, one per body (written by
   unsigned long long total;         // entries the cell lists would need
 };
 
-static size_t ms_align(size_t x) { return (x + 255) & ~(size_t)255; }
-struct MsWs {
+struct MsWs {                       // the layout of mh_cells_p.h
   MsHdr* hdr;                       // [B]
   int* start;                       // [B][MS_MAX_CELLS + 1]
   int* cursor;                      // [B][MS_MAX_CELLS]
   float4* rec;                      // [B][F][3]   (x, y, z, valid) of the three corners; valid in the first only
   int* list;                        // [B][MS_CAP_PER_FACE F]   faces by cell
 };
-static size_t ms_bytes(size_t B, size_t F) {
-  return ms_align(B * sizeof(MsHdr)) + ms_align(B * (MS_MAX_CELLS + 1) * 4) + ms_align(B * MS_MAX_CELLS * 4) + ms_align(B * F * 48) +
-         ms_align(B * F * MS_CAP_PER_FACE * 4);
-}
+static size_t ms_bytes(size_t B, size_t F) { return cells_bytes(B, sizeof(MsHdr), MS_MAX_CELLS, B * F * 48, B * F * MS_CAP_PER_FACE * 4); }
 static MsWs ms_carve(void* ws, size_t B, size_t F) {
-  char* c = (char*)ws;
-  MsWs w;
-  w.hdr = (MsHdr*)c; c += ms_align(B * sizeof(MsHdr));
-  w.start = (int*)c; c += ms_align(B * (MS_MAX_CELLS + 1) * 4);
-  w.cursor = (int*)c; c += ms_align(B * MS_MAX_CELLS * 4);
-  w.rec = (float4*)c; c += ms_align(B * F * 48);
-  w.list = (int*)c;
-  return w;
+  const CellsWs c = cells_carve(ws, B, sizeof(MsHdr), MS_MAX_CELLS, B * F * 48);
+  return {(MsHdr*)c.hdr, c.start, c.cursor, (float4*)c.a, (int*)c.b};
 }
 
 __device__ __forceinline__ bool ms_finite(float x) { return fabsf(x) < INFINITY; }            // (false for NaN)
@@ -121,7 +112,6 @@ __device__ __forceinline__ bool ms_sane(const MsHdr& h) {                       
 // ---- build: boxes, face records and totals, counts, scan, fill ----------------------------------------------------------------
 // one workgroup per body: the box of its finite vertices, the grid's shape, and the cleared counts
 __global__ __launch_bounds__(MS_BLOCK) void k_ms_setup(int V, int F, const float* verts, const uint8_t* live, MsHdr* hdrs, int* start) {
-  __shared__ float smn[3][MS_BLOCK / 64], smx[3][MS_BLOCK / 64];
   __shared__ int s_nc;
   const size_t b = blockIdx.x;
   const int tid = threadIdx.x;
@@ -135,20 +125,8 @@ __global__ __launch_bounds__(MS_BLOCK) void k_ms_setup(int V, int F, const float
 #pragma unroll
       for (int c = 0; c < 3; ++c) { mn[c] = fminf(mn[c], p[c]); mx[c] = fmaxf(mx[c], p[c]); }
     }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      mn[c] = fminf(mn[c], __shfl_xor(mn[c], o, 64));
-      mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], o, 64));
-    }
-  }
-  if ((tid & 63) == 0)
-    for (int c = 0; c < 3; ++c) { smn[c][tid >> 6] = mn[c]; smx[c][tid >> 6] = mx[c]; }
-  __syncthreads();
+  cells_box_reduce<MS_BLOCK>(mn, mx);
   if (tid == 0) {
-    for (int w = 1; w < MS_BLOCK / 64; ++w)
-      for (int c = 0; c < 3; ++c) { mn[c] = fminf(mn[c], smn[c][w]); mx[c] = fmaxf(mx[c], smx[c][w]); }
     MsHdr h;
     h.flags = alive ? 0 : MS_NOT_LIVE;
     h.overflow = 0;
@@ -188,23 +166,35 @@ __global__ __launch_bounds__(MS_BLOCK) void k_ms_setup(int V, int F, const float
   for (int i = tid; i <= nc; i += MS_BLOCK) counts[i] = 0;
 }
 
-// the cells [c0, c1] per axis that the box of a face record overlaps
-__device__ __forceinline__ void ms_face_cells(const MsHdr& h, const float4 a, const float4 b, const float4 c, int c0[3], int c1[3]) {
-  const float lo[3] = {fminf(a.x, fminf(b.x, c.x)), fminf(a.y, fminf(b.y, c.y)), fminf(a.z, fminf(b.z, c.z))};
-  const float hi[3] = {fmaxf(a.x, fmaxf(b.x, c.x)), fmaxf(a.y, fmaxf(b.y, c.y)), fmaxf(a.z, fmaxf(b.z, c.z))};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    c0[k] = ms_cell(lo[k], h.mn[k], h.inv, h.d[k]);
-    c1[k] = max(ms_cell(hi[k], h.mn[k], h.inv, h.d[k]), c0[k]);
-  }
+__device__ __forceinline__ bool ms_walks_all(const MsHdr& h, int F, int force) {
+  return force != 0 || h.overflow != 0 || cells_over_cap(h.total, F, MS_CAP_PER_FACE);
 }
+
+struct MsGrid {                     // the face grid of mh_cells_p.h: three-dimensional
+  typedef MsHdr Hdr;
+  typedef float4 Rec;
+  static constexpr int BLOCK = MS_BLOCK, MAX_CELLS = MS_MAX_CELLS, CAP_PER_FACE = MS_CAP_PER_FACE;
+  static __device__ __forceinline__ bool counted(const MsHdr& h, int F, int force) { return !(h.flags & MS_NOT_LIVE) && !ms_walks_all(h, F, force); }
+  static __device__ __forceinline__ bool valid(const float4& r) { return r.w != 0.f; }
+  // the cells [c0, c1] per axis that the box of a face record overlaps
+  static __device__ __forceinline__ void range(const MsHdr& h, const float4 a, const float4 b, const float4 c, int c0[3], int c1[3]) {
+    const float lo[3] = {fminf(a.x, fminf(b.x, c.x)), fminf(a.y, fminf(b.y, c.y)), fminf(a.z, fminf(b.z, c.z))};
+    const float hi[3] = {fmaxf(a.x, fmaxf(b.x, c.x)), fmaxf(a.y, fmaxf(b.y, c.y)), fmaxf(a.z, fmaxf(b.z, c.z))};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      c0[k] = ms_cell(lo[k], h.mn[k], h.inv, h.d[k]);
+      c1[k] = max(ms_cell(hi[k], h.mn[k], h.inv, h.d[k]), c0[k]);
+    }
+  }
+  static __device__ __forceinline__ int cell(const MsHdr& h, int cx, int cy, int cz) { return (cz * h.d[1] + cy) * h.d[0] + cx; }
+};
 
 // one lane per (body, face), the workgroups of a body consecutive: the face's record, and the entries it would need
 __global__ __launch_bounds__(MS_BLOCK) void k_ms_faces(int V, int F, int fpb, const float* verts, const int* faces, MsHdr* hdrs, float4* rec) {
   __shared__ int s_total;
   const int tid = threadIdx.x;
-  const size_t b = blockIdx.x / fpb;
-  const int f = (int)(blockIdx.x - b * fpb) * MS_BLOCK + tid;
+  size_t b;
+  const int f = cells_body_face<MS_BLOCK>(fpb, b);
   if (tid == 0) s_total = 0;
   __syncthreads();
   const MsHdr h = hdrs[b];
@@ -228,7 +218,7 @@ __global__ __launch_bounds__(MS_BLOCK) void k_ms_faces(int V, int F, int fpb, co
     o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
     if (ok && !h.overflow) {
       int c0[3], c1[3];
-      ms_face_cells(h, r[0], r[1], r[2], c0, c1);
+      MsGrid::range(h, r[0], r[1], r[2], c0, c1);
       atomicAdd(&s_total, (c1[0] - c0[0] + 1) * (c1[1] - c0[1] + 1) * (c1[2] - c0[2] + 1));      // (<= 256 x 8192: no overflow)
     }
   }
@@ -236,32 +226,10 @@ __global__ __launch_bounds__(MS_BLOCK) void k_ms_faces(int V, int F, int fpb, co
   if (tid == 0 && s_total != 0) atomicAdd(&hdrs[b].total, (unsigned long long)s_total);
 }
 
-__device__ __forceinline__ bool ms_walks_all(const MsHdr& h, int F, int force) {
-  return force != 0 || h.overflow != 0 || h.total > (unsigned long long)MS_CAP_PER_FACE * (unsigned long long)F;
-}
-
-// one lane per (body, face): the face counted in every cell of its box (grid-path bodies only: at most 16 F atomics a body)
-__global__ __launch_bounds__(MS_BLOCK) void k_ms_count(int F, int fpb, int force, const MsHdr* hdrs, const float4* rec, int* start) {
-  const size_t b = blockIdx.x / fpb;
-  const int f = (int)(blockIdx.x - b * fpb) * MS_BLOCK + threadIdx.x;
-  if (f >= F) return;
-  const MsHdr h = hdrs[b];
-  if ((h.flags & MS_NOT_LIVE) || ms_walks_all(h, F, force)) return;
-  const float4* r = rec + (b * F + f) * 3;
-  const float4 p0 = r[0], p1 = r[1], p2 = r[2];
-  if (p0.w == 0.f) return;
-  int c0[3], c1[3];
-  ms_face_cells(h, p0, p1, p2, c0, c1);
-  int* counts = start + b * (MS_MAX_CELLS + 1);
-  for (int cz = c0[2]; cz <= c1[2]; ++cz)
-    for (int cy = c0[1]; cy <= c1[1]; ++cy)
-      for (int cx = c0[0]; cx <= c1[0]; ++cx) atomicAdd(&counts[(cz * h.d[1] + cy) * h.d[0] + cx], 1);
-}
+// (the counts and the fill are k_cells_count<MsGrid> and k_cells_fill<MsGrid>: at most 16 F atomics a body)
 
 // one workgroup per body: the path it takes and its status word; exclusive scan of its counts in place, and the fill cursors
 __global__ __launch_bounds__(1024) void k_ms_scan(int F, int force, MsHdr* hdrs, int* start, int* cursor, int* status) {
-  __shared__ int swave[16];
-  __shared__ int carry;
   const size_t b = blockIdx.x;
   const MsHdr h = hdrs[b];
   const bool alive = (h.flags & MS_NOT_LIVE) == 0;
@@ -270,53 +238,9 @@ __global__ __launch_bounds__(1024) void k_ms_scan(int F, int force, MsHdr* hdrs,
     const int flags = h.flags | (all ? MS_ALL_FACES : 0);
     hdrs[b].flags = flags;
     if (status) status[b] = flags;
-    carry = 0;
   }
   if (!alive || all) return;                               // (uniform over the workgroup)
-  int* counts = start + b * (MS_MAX_CELLS + 1);
-  int* cur = cursor + b * MS_MAX_CELLS;
-  const int nc = min(h.d[0] * h.d[1] * h.d[2], MS_MAX_CELLS), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  for (int base = 0; base < nc; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = i < nc ? counts[i] : 0;
-    const int incl = mh_wave_scan_add(v);
-    if (lane == 63) swave[wave] = incl;
-    __syncthreads();
-    int woff = carry;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) woff += (w < wave) ? swave[w] : 0;
-    if (i < nc) {
-      counts[i] = woff + incl - v;
-      cur[i] = woff + incl - v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = woff + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[nc] = carry;
-}
-
-__global__ __launch_bounds__(MS_BLOCK) void k_ms_fill(int F, int fpb, const MsHdr* hdrs, const float4* rec, int* cursor, int* list) {
-  const size_t b = blockIdx.x / fpb;
-  const int f = (int)(blockIdx.x - b * fpb) * MS_BLOCK + threadIdx.x;
-  if (f >= F) return;
-  const MsHdr h = hdrs[b];
-  if (h.flags != 0) return;                                // dead, or walking all faces
-  const float4* r = rec + (b * F + f) * 3;
-  const float4 p0 = r[0], p1 = r[1], p2 = r[2];
-  if (p0.w == 0.f) return;
-  int c0[3], c1[3];
-  ms_face_cells(h, p0, p1, p2, c0, c1);
-  int* cur = cursor + b * MS_MAX_CELLS;
-  int* lst = list + b * (size_t)F * MS_CAP_PER_FACE;
-  const long long cap = (long long)F * MS_CAP_PER_FACE;
-  for (int cz = c0[2]; cz <= c1[2]; ++cz)
-    for (int cy = c0[1]; cy <= c1[1]; ++cy)
-      for (int cx = c0[0]; cx <= c1[0]; ++cx) {
-        const int pos = atomicAdd(&cur[(cz * h.d[1] + cy) * h.d[0] + cx], 1);
-        if (pos >= 0 && pos < cap) lst[pos] = f;           // (cannot miss after the count; a lane never leaves its body's slab)
-      }
+  cells_scan_1024(min(h.d[0] * h.d[1] * h.d[2], MS_MAX_CELLS), start + b * (MS_MAX_CELLS + 1), cursor + b * MS_MAX_CELLS);
 }
 
 // ---- the visit of one face: the header's formula, in its order ------------------------------------------------------------------
@@ -395,7 +319,6 @@ __device__ __forceinline__ bool ms_search(const MsHdr& h, int F, const float4* _
     cq[a] = ms_cell(q[a], h.mn[a], h.inv, h.d[a]);
     K = max(K, max(cq[a], h.d[a] - 1 - cq[a]));
   }
-  const long long cap = (long long)F * MS_CAP_PER_FACE;
   for (int k = 0; k <= K; ++k) {                           // K < MS_MAX_DIM rings, every cell of the grid at most once
     const int z0 = max(cq[2] - k, 0), z1 = min(cq[2] + k, h.d[2] - 1);
     const int y0 = max(cq[1] - k, 0), y1 = min(cq[1] + k, h.d[1] - 1);
@@ -415,12 +338,7 @@ __device__ __forceinline__ bool ms_search(const MsHdr& h, int F, const float4* _
           const float gx = ms_slab_gap(h, 0, cx, q[0], slack);
           if (gzy + gx * gx > fminf(best.d2, r2)) continue; // the cell
           const int c = (cz * h.d[1] + cy) * h.d[0] + cx;
-          const int a = max(start[c], 0);
-          const int e = (int)min((long long)start[c + 1], cap);
-          for (int i = a; i < e; ++i) {
-            const int f = list[i];
-            if ((unsigned)f < (unsigned)F) ms_face(rec + (size_t)f * 3, f, q, r2, best, visits);
-          }
+          cells_visit(start, list, c, F, MS_CAP_PER_FACE, [&](int f) { ms_face(rec + (size_t)f * 3, f, q, r2, best, visits); });
         }
       }
     }
@@ -638,11 +556,11 @@ extern "C" int mh_surface_grid(int B, int V, int F, const float* verts, const in
   MH_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_ms_faces, dim3(nblk), dim3(MS_BLOCK), 0, st, V, F, fpb, verts, faces, w.hdr, w.rec);
   MH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ms_count, dim3(nblk), dim3(MS_BLOCK), 0, st, F, fpb, force, (const MsHdr*)w.hdr, (const float4*)w.rec, w.start);
+  hipLaunchKernelGGL(k_cells_count<MsGrid>, dim3(nblk), dim3(MS_BLOCK), 0, st, F, fpb, force, (const MsHdr*)w.hdr, (const float4*)w.rec, w.start);
   MH_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_ms_scan, dim3((unsigned)B), dim3(1024), 0, st, F, force, w.hdr, w.start, w.cursor, status);
   MH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ms_fill, dim3(nblk), dim3(MS_BLOCK), 0, st, F, fpb, (const MsHdr*)w.hdr, (const float4*)w.rec, w.cursor, w.list);
+  hipLaunchKernelGGL(k_cells_fill<MsGrid>, dim3(nblk), dim3(MS_BLOCK), 0, st, F, fpb, (const MsHdr*)w.hdr, (const float4*)w.rec, w.cursor, w.list);
   MH_LAUNCH_CHECK();
   return MH_OK;
 }

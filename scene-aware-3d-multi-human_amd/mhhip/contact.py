@@ -6,33 +6,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-
-PART_NAMES = ('pelvis', 'left_hip', 'right_hip', 'spine1', 'left_knee', 'right_knee', 'spine2', 'left_ankle', 'right_ankle', 'spine3',
-              'left_foot', 'right_foot', 'neck', 'left_collar', 'right_collar', 'head', 'left_shoulder', 'right_shoulder', 'left_elbow',
-              'right_elbow', 'left_wrist', 'right_wrist', 'left_hand', 'right_hand')
-MAX_RADIUS = 0.64           # MH_SCENE_NEAREST_MAX_CELLS (32) cells of the smallest grid cell (0.02 m)
-
-
-def body_parts(model):
-    """(V,) uint8: the joint with the largest skinning weight of every vertex, the first one on ties.  ``model``: a body model
-    (``lbs_weights``), an SMPL data struct (``weights``), or the (V,J) weights themselves, J <= 32."""
-    w = model
-    for name in ('lbs_weights', 'weights'):
-        if hasattr(w, name):
-            w = getattr(w, name)
-            break
-    w = w.toarray() if hasattr(w, 'toarray') else w
-    w = np.asarray(w.detach().cpu() if isinstance(w, torch.Tensor) else w)
-    if w.ndim != 2 or w.shape[0] == 0 or not 1 <= w.shape[1] <= 32:
-        raise ValueError('skinning weights must be (V,J) with 1 <= J <= 32, got %s' % (tuple(w.shape),))
-    return np.argmax(w, axis=1).astype(np.uint8)          # numpy's argmax keeps the first of equal entries
-
-
-def _radius(radius):
-    r = float(np.float32(radius))
-    if not (np.isfinite(r) and 0.0 < r <= MAX_RADIUS):
-        raise ValueError('radius must be positive and at most %.2f m (the kernel walks every cell within it), got %r' % (MAX_RADIUS, radius))
-    return r
+from .bodies import MAX_RADIUS, PART_NAMES, body_parts, cell_radius, contact_within, part_table  # noqa: F401 (names of this module too)
 
 
 def _grid(L, pts, st):
@@ -55,7 +29,7 @@ def scene_nearest(points, queries, radius):
     """points (M,3), queries (Q,3) on the device -> (d2 (Q), nearest (Q,3)): squared distance to and position of the nearest
     point within ``radius`` (include/mhmocap_hip.h has the definition); +inf and (0,0,0) where there is none.  Builds a grid
     of its own over ``points``."""
-    radius = _radius(radius)
+    radius = cell_radius(radius)
     if queries.dim() != 2 or queries.shape[-1] != 3 or int(queries.shape[0]) == 0:
         raise ValueError('queries must be (Q,3) with Q > 0, got %s' % (tuple(queries.shape),))
     dev = queries.device
@@ -86,24 +60,16 @@ def contact_map(model, verts, scene_points, radius=0.1, contact=0.03, nearest=Fa
     if verts.dim() != 4 or verts.shape[-1] != 3 or 0 in verts.shape:
         raise ValueError('verts must be (T,N,V,3), got %s' % (tuple(verts.shape),))
     T, N, V = int(verts.shape[0]), int(verts.shape[1]), int(verts.shape[2])
-    radius = _radius(radius)
-    contact = float(np.float32(contact))
-    if not 0.0 <= contact <= radius:
-        raise ValueError('contact must lie in [0, radius = %g]: beyond the radius no distance is known, got %g' % (radius, contact))
-    part = body_parts(model)
-    if part.shape[0] != V:
-        raise ValueError('the model has %d vertices, verts %d' % (part.shape[0], V))
-    P = len(PART_NAMES)
-    if int(part.max()) >= P:
-        raise ValueError('the model has more than %d parts' % P)
-    chunk = max(1, min(int(chunk), T))
+    radius = cell_radius(radius)
+    contact = contact_within(contact, radius)
     dev = verts.device
+    part, P = part_table(model, V, dev)
+    chunk = max(1, min(int(chunk), T))
     L = _lib.lib()
     with torch.cuda.device(dev), torch.no_grad():
         st = _lib.stream_ptr(dev)
         pts = _cloud(scene_points, dev)
         verts = verts.contiguous().float()
-        part = torch.as_tensor(part).to(dev)
         grid, M = _grid(L, pts, st)
         d2 = torch.empty(T, N, V, dtype=torch.float32, device=dev)
         near = torch.empty(T, N, V, 3, dtype=torch.float32, device=dev) if nearest else None

@@ -3,41 +3,14 @@ every vertex of every person the other people of its frame that contain it, how 
 per pair of people and per body part (``mh_person_inside``).  The test is defined on an integer lattice of 2^-16 m, so it is
 exact and the same on every launch.  Read-only: a workspace and buffers of its own, nothing of an engine's state is written.
 include/mhmocap_hip.h has the definitions; the parts are those of ``mhhip.contact``."""
-import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .contact import PART_NAMES, body_parts
+from .bodies import MAX_PEOPLE, PART_NAMES, batch_shape, body_parts, faces as model_faces, live_mask, part_table, shape  # noqa: F401
 
-MAX_PEOPLE = 32
 LATTICE_M = 2.0 ** -16                  # metres per lattice unit
 NOT_LIVE, NOT_TESTABLE, ALL_FACES = 1, 2, 4     # bits of the status word
-
-
-def _faces_of(model):
-    for name in ('faces', 'f'):
-        if hasattr(model, name):
-            return np.asarray(getattr(model, name))
-    return np.asarray(model)
-
-
-def _faces(model, dev):
-    """(F,3) int32 on ``dev``; kept on the model where it can keep them"""
-    cache = getattr(model, '_inside_faces', None)
-    if cache is not None and str(dev) in cache:
-        return cache[str(dev)]
-    faces = _faces_of(model)
-    if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
-        raise ValueError('faces must be (F,3), got %s' % (tuple(faces.shape),))
-    tab = torch.as_tensor(np.ascontiguousarray(faces, dtype=np.int32)).to(dev)
-    try:
-        if cache is None:
-            cache = model._inside_faces = {}
-        cache[str(dev)] = tab
-    except AttributeError:                                  # (an array of faces: nothing to keep them on)
-        pass
-    return tab
 
 
 def _metres(lat):
@@ -56,23 +29,13 @@ def mesh_winding(verts, faces, points, live=None):
     """verts (B,V,3), points (B,Q,3) on the device, faces (F,3) integers (or a body model), live (B) or None -> the raw
     results of ``mh_mesh_bins`` and ``mh_mesh_winding``: (winding, up, down (B,Q) int32 in lattice units, -1 = none,
     status (B) int32)"""
-    if verts.dim() != 3 or verts.shape[-1] != 3 or 0 in verts.shape:
-        raise ValueError('verts must be (V,3) or (B,V,3), got %s' % (tuple(verts.shape),))
-    B, V = int(verts.shape[0]), int(verts.shape[1])
-    if points.dim() != 3 or points.shape[-1] != 3 or 0 in points.shape or points.shape[0] != B:
-        raise ValueError('points must be (Q,3) for verts (V,3) or (B,Q,3) for verts (B,V,3), got %s' % (tuple(points.shape),))
-    Q = int(points.shape[1])
-    lv = None
-    if live is not None:
-        lv = torch.as_tensor(live)
-        if tuple(lv.shape) != (B,):
-            raise ValueError('live must be (B) = (%d), got %s' % (B, tuple(lv.shape)))
-        lv = (lv != 0).to(torch.uint8)
+    B, V, Q = batch_shape(verts, points)
+    lv = live_mask(live, B)
     dev = verts.device
     L = _lib.lib()
     with torch.cuda.device(dev), torch.no_grad():
         st = _lib.stream_ptr(dev)
-        fc = _faces(faces, dev)
+        fc = model_faces(faces, dev)
         F = int(fc.shape[0])
         lv = None if lv is None else lv.to(dev).contiguous()
         v = verts.contiguous().float()
@@ -104,25 +67,6 @@ def points_inside_mesh(verts, faces, points):
     return tuple(o[0] for o in out) if single else out
 
 
-def _shape(verts):
-    if verts.dim() != 4 or verts.shape[-1] != 3 or 0 in verts.shape:
-        raise ValueError('verts must be (T,N,V,3), got %s' % (tuple(verts.shape),))
-    T, N, V = int(verts.shape[0]), int(verts.shape[1]), int(verts.shape[2])
-    if N > MAX_PEOPLE:
-        raise ValueError('at most %d people per frame, got %d' % (MAX_PEOPLE, N))
-    return T, N, V
-
-
-def _live(live, T, N):
-    """(T,N) uint8 on the host, or None"""
-    if live is None:
-        return None
-    lv = torch.as_tensor(live)
-    if tuple(lv.shape) != (T, N):
-        raise ValueError('live must be (T,N) = (%d,%d), got %s' % (T, N, tuple(lv.shape)))
-    return (lv != 0).to(torch.uint8)
-
-
 def penetration_map(model, verts, live=None, chunk=8):
     """verts (T,N,V,3) on the device, any frame whose z is the axis depth is to be measured along (the fit's camera frame);
     live (T,N): the people that are there -> dict of device tensors:
@@ -139,23 +83,17 @@ def penetration_map(model, verts, live=None, chunk=8):
 
     ``chunk`` frames go into one call; memory beyond the inputs and outputs is the workspace of one chunk.  One person per
     frame is not an error: everything is inf / -1 / 0."""
-    T, N, V = _shape(verts)
-    part = body_parts(model)
-    if part.shape[0] != V:
-        raise ValueError('the model has %d vertices, verts %d' % (part.shape[0], V))
-    P = len(PART_NAMES)
-    if int(part.max()) >= P:
-        raise ValueError('the model has more than %d parts' % P)
-    lv = _live(live, T, N)
-    chunk = max(1, min(int(chunk), T))
+    T, N, V = shape(verts)
     dev = verts.device
+    part, P = part_table(model, V, dev)
+    lv = live_mask(live, T, N)
+    chunk = max(1, min(int(chunk), T))
     L = _lib.lib()
     with torch.cuda.device(dev), torch.no_grad():
         st = _lib.stream_ptr(dev)
         lv = None if lv is None else lv.to(dev).contiguous()
         verts = verts.contiguous().float()
-        part = torch.as_tensor(part).to(dev)
-        faces = _faces(model, dev)
+        faces = model_faces(model, dev)
         F = int(faces.shape[0])
         nbytes = L.mh_mesh_bins_bytes(chunk * N, F)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)

@@ -8,52 +8,8 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .contact import MAX_RADIUS, PART_NAMES, _radius, body_parts
-
-MAX_PEOPLE = 32
-
-
-def vertex_faces(faces, V):
-    """faces (F,3) integers, V -> (adj_start (V+1) int32, adj_face (A) int32): for vertex v the faces
-    ``adj_face[adj_start[v]:adj_start[v+1]]`` that name it, in ascending face index, a face once per corner that names the
-    vertex.  Corners that name a vertex outside [0, V) are left out (the kernel skips such a face altogether)."""
-    faces = np.asarray(faces)
-    if faces.ndim != 2 or faces.shape[1] != 3 or int(V) <= 0:
-        raise ValueError('faces must be (F,3) and V positive, got %s and %r' % (tuple(faces.shape), V))
-    V = int(V)
-    corner = faces.astype(np.int64).reshape(-1)
-    face = np.repeat(np.arange(faces.shape[0], dtype=np.int64), 3)
-    keep = (corner >= 0) & (corner < V)
-    corner, face = corner[keep], face[keep]
-    order = np.argsort(corner, kind='stable')             # stable: the faces of a vertex stay in ascending order
-    adj_start = np.zeros(V + 1, np.int32)
-    adj_start[1:] = np.cumsum(np.bincount(corner, minlength=V))
-    return adj_start, face[order].astype(np.int32)
-
-
-def _faces_of(model):
-    for name in ('faces', 'f'):
-        if hasattr(model, name):
-            return np.asarray(getattr(model, name))
-    return np.asarray(model)
-
-
-def _tables(model, V, dev):
-    """(faces (F,3) int32, adj_start, adj_face) on ``dev``; built once per model and device where the model can keep them"""
-    key = (str(dev), V)
-    cache = getattr(model, '_proximity_tables', None)
-    if cache is not None and key in cache:
-        return cache[key]
-    faces = _faces_of(model)
-    adj_start, adj_face = vertex_faces(faces, V)
-    tabs = tuple(torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev) for a in (faces, adj_start, adj_face))
-    try:
-        if cache is None:
-            cache = model._proximity_tables = {}
-        cache[key] = tabs
-    except AttributeError:                                  # (an array of faces: nothing to keep them on)
-        pass
-    return tabs
+from .bodies import (MAX_PEOPLE, MAX_RADIUS, PART_NAMES, adjacency, body_parts, cell_radius, contact_within,  # noqa: F401
+                     live_mask, part_table, shape, vertex_faces)
 
 
 def vertex_normals(model, verts):
@@ -66,7 +22,7 @@ def vertex_normals(model, verts):
     L = _lib.lib()
     with torch.cuda.device(dev), torch.no_grad():
         st = _lib.stream_ptr(dev)
-        faces, adj_start, adj_face = _tables(model, V, dev)
+        faces, adj_start, adj_face = adjacency(model, V, dev)
         v = verts.contiguous().float()
         out = torch.empty_like(v)
         check(L.mh_vertex_normals(v.numel() // (3 * V), V, int(faces.shape[0]), ptr(v), ptr(faces), ptr(adj_start), ptr(adj_face),
@@ -74,32 +30,13 @@ def vertex_normals(model, verts):
     return out
 
 
-def _shape(verts):
-    if verts.dim() != 4 or verts.shape[-1] != 3 or 0 in verts.shape:
-        raise ValueError('verts must be (T,N,V,3), got %s' % (tuple(verts.shape),))
-    T, N, V = int(verts.shape[0]), int(verts.shape[1]), int(verts.shape[2])
-    if N > MAX_PEOPLE:
-        raise ValueError('at most %d people per frame, got %d' % (MAX_PEOPLE, N))
-    return T, N, V
-
-
-def _live(live, T, N):
-    """(T,N) uint8 on the host, or None"""
-    if live is None:
-        return None
-    lv = torch.as_tensor(live)
-    if tuple(lv.shape) != (T, N):
-        raise ValueError('live must be (T,N) = (%d,%d), got %s' % (T, N, tuple(lv.shape)))
-    return (lv != 0).to(torch.uint8)
-
-
 def person_nearest(verts, radius, live=None):
     """verts (T,N,V,3) on the device -> (d2 (T,N,V) float32, idx (T,N,V) int32): squared distance to the nearest vertex of
     another live person of the same frame within ``radius`` and its index m V + u; +inf and -1 where there is none
     (``mh_person_nearest``).  ``live`` (T,N): people that are there, default all."""
-    T, N, V = _shape(verts)
-    radius = _radius(radius)
-    lv = _live(live, T, N)
+    T, N, V = shape(verts)
+    radius = cell_radius(radius)
+    lv = live_mask(live, T, N)
     dev = verts.device
     L = _lib.lib()
     with torch.cuda.device(dev), torch.no_grad():
@@ -147,27 +84,19 @@ def proximity_map(model, verts, live=None, radius=0.1, contact=0.02, nearest=Fal
 
     ``chunk`` frames go into one call; memory beyond the inputs and outputs is the workspace and normals of one chunk.  One
     person per frame is not an error: everything is inf / -1 / 0."""
-    T, N, V = _shape(verts)
-    radius = _radius(radius)
-    contact = float(np.float32(contact))
-    if not 0.0 <= contact <= radius:
-        raise ValueError('contact must lie in [0, radius = %g]: beyond the radius no distance is known, got %g' % (radius, contact))
-    part = body_parts(model)
-    if part.shape[0] != V:
-        raise ValueError('the model has %d vertices, verts %d' % (part.shape[0], V))
-    P = len(PART_NAMES)
-    if int(part.max()) >= P:
-        raise ValueError('the model has more than %d parts' % P)
-    lv = _live(live, T, N)
-    chunk = max(1, min(int(chunk), T))
+    T, N, V = shape(verts)
+    radius = cell_radius(radius)
+    contact = contact_within(contact, radius)
     dev = verts.device
+    part, P = part_table(model, V, dev)
+    lv = live_mask(live, T, N)
+    chunk = max(1, min(int(chunk), T))
     L = _lib.lib()
     with torch.cuda.device(dev), torch.no_grad():
         st = _lib.stream_ptr(dev)
         lv = None if lv is None else lv.to(dev).contiguous()
         verts = verts.contiguous().float()
-        part = torch.as_tensor(part).to(dev)
-        faces, adj_start, adj_face = _tables(model, V, dev)
+        faces, adj_start, adj_face = adjacency(model, V, dev)
         nbytes = L.mh_person_nearest_bytes(chunk, N, V)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         normals = torch.empty(chunk, N, V, 3, dtype=torch.float32, device=dev)

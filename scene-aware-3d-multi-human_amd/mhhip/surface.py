@@ -5,13 +5,12 @@ inside one of them -- with the closest surface point and the tables per pair of 
 (``mh_person_surface``, ``mh_surface_pairs``).  The distance is defined in float32 in a fixed order, so it is the same on every
 launch and equal bit for bit to a float32 evaluation on the host.  Read-only: a workspace and buffers of its own, nothing of an
 engine's state is written.  include/mhmocap_hip.h has the definitions; the parts are those of ``mhhip.contact``."""
-import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .contact import PART_NAMES, _radius, body_parts
-from .inside import _faces, _live, _shape
+from .bodies import (PART_NAMES, any_radius, batch_shape, body_parts, cell_radius, contact_within, faces as model_faces,  # noqa: F401
+                     live_mask, part_table, shape)
 
 NOT_LIVE, NOT_TESTABLE, ALL_FACES = 1, 2, 4     # bits of the status word
 INF = float('inf')
@@ -23,35 +22,18 @@ def force_all_faces(on):
     return bool(_lib.lib().mh_surface_set_all_faces(1 if on else 0))
 
 
-def _any_radius(radius):
-    r = float(np.float32(radius))
-    if not r > 0.0:                                         # (NaN, zero, negative, -inf)
-        raise ValueError('radius must be positive (inf is allowed), got %r' % (radius,))
-    return r
-
-
 def mesh_closest(verts, faces, points, radius=INF, live=None):
     """verts (B,V,3), points (B,Q,3) on the device, faces (F,3) integers (or a body model), live (B) or None -> the raw
     results of ``mh_surface_grid`` and ``mh_mesh_closest``: (d2 (B,Q) float32, face (B,Q) int32, point, weights (B,Q,3)
     float32, status (B) int32)"""
-    if verts.dim() != 3 or verts.shape[-1] != 3 or 0 in verts.shape:
-        raise ValueError('verts must be (V,3) or (B,V,3), got %s' % (tuple(verts.shape),))
-    B, V = int(verts.shape[0]), int(verts.shape[1])
-    if points.dim() != 3 or points.shape[-1] != 3 or 0 in points.shape or points.shape[0] != B:
-        raise ValueError('points must be (Q,3) for verts (V,3) or (B,Q,3) for verts (B,V,3), got %s' % (tuple(points.shape),))
-    Q = int(points.shape[1])
-    radius = _any_radius(radius)
-    lv = None
-    if live is not None:
-        lv = torch.as_tensor(live)
-        if tuple(lv.shape) != (B,):
-            raise ValueError('live must be (B) = (%d), got %s' % (B, tuple(lv.shape)))
-        lv = (lv != 0).to(torch.uint8)
+    B, V, Q = batch_shape(verts, points)
+    radius = any_radius(radius)
+    lv = live_mask(live, B)
     dev = verts.device
     L = _lib.lib()
     with torch.cuda.device(dev), torch.no_grad():
         st = _lib.stream_ptr(dev)
-        fc = _faces(faces, dev)
+        fc = model_faces(faces, dev)
         F = int(fc.shape[0])
         lv = None if lv is None else lv.to(dev).contiguous()
         v = verts.contiguous().float()
@@ -136,27 +118,19 @@ def clearance_map(model, verts, live=None, radius=0.1, contact=0.02, nearest=Fal
 def _clearance(model, verts, live, radius, contact, nearest, chunk, stats):
     """``clearance_map``; ``stats`` adds ``searched`` and ``faces_visited`` (T,N,V) i32: the other bodies a vertex searched (not
     dropped at their box) and the faces it evaluated (tools/clearance_map.py reports them)"""
-    T, N, V = _shape(verts)
-    radius = _radius(radius)
-    contact = float(np.float32(contact))
-    if not 0.0 <= contact <= radius:
-        raise ValueError('contact must lie in [0, radius = %g]: beyond the radius no distance is known, got %g' % (radius, contact))
-    part = body_parts(model)
-    if part.shape[0] != V:
-        raise ValueError('the model has %d vertices, verts %d' % (part.shape[0], V))
-    P = len(PART_NAMES)
-    if int(part.max()) >= P:
-        raise ValueError('the model has more than %d parts' % P)
-    lv = _live(live, T, N)
-    chunk = max(1, min(int(chunk), T))
+    T, N, V = shape(verts)
+    radius = cell_radius(radius)
+    contact = contact_within(contact, radius)
     dev = verts.device
+    part, P = part_table(model, V, dev)
+    lv = live_mask(live, T, N)
+    chunk = max(1, min(int(chunk), T))
     L = _lib.lib()
     with torch.cuda.device(dev), torch.no_grad():
         st = _lib.stream_ptr(dev)
         lv = None if lv is None else lv.to(dev).contiguous()
         verts = verts.contiguous().float()
-        part = torch.as_tensor(part).to(dev)
-        faces = _faces(model, dev)
+        faces = model_faces(model, dev)
         F = int(faces.shape[0])
         nb_in, nb_sf = L.mh_mesh_bins_bytes(chunk * N, F), L.mh_surface_grid_bytes(chunk * N, F)
         ws_in = torch.empty(nb_in, dtype=torch.uint8, device=dev)

@@ -32,6 +32,15 @@ except Exception:  # pragma: no cover
     tqdm = None
 
 
+def frames_arg(frames, T):
+    """The ``frames`` argument of the diagnostics as int64 indices into a sequence of ``T`` frames: all of them for None,
+    else the caller's, in the caller's order and with its duplicates."""
+    idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
+    if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
+        raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
+    return idx.astype(np.int64)
+
+
 class SMPLOptimizerBase(object):
     """reference optimizer.py:32-143"""
     _needs_hip = True          # there is no CPU path (tests/cpu_shard_engine.py subclasses this for the gloo orchestration tests)
@@ -677,6 +686,51 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
             'scene_mask': self.scene_mask if hasattr(self, 'scene_mask') else None,
         }
 
+    # -- what the diagnostics below share: their checks, and their loop over the frames -----------------------------------
+    def _diag_frames(self, name, verb, frames, chunk, need=None):
+        """What every diagnostic checks first, in this order: there is an engine, the run is not frame-sharded, the method's
+        own precondition (``need()`` raises), ``frames``.  ``verb`` is 'render from' / 'report on' / 'measure on'.  Returns
+        the frame indices (``frames_arg``) and ``chunk`` as at least 1."""
+        if self.engine is None:
+            raise RuntimeError('%s: nothing to %s before init_optimized_variables()' % (name, verb.split()[0]))
+        if self._world()[0] > 1:
+            raise RuntimeError('%s is not available in a frame-sharded run (world > 1): %s the gathered '
+                               'result of get_optimized_variables() in one process' % (name, verb))
+        if need is not None:
+            need()
+        return frames_arg(frames, self.num_frames), max(1, int(chunk))
+
+    def _diag_chunks(self, idx, chunk, call, prev=False):
+        """The loop of every diagnostic over the frames ``idx``, ``chunk`` at a time: the vertices of ``predict`` (LBS, scale,
+        translation) of the current leaves at ``idx[sl]`` as (n, N, V, 3), ``call(sl, verts)`` -> dict of tensors, the dicts
+        concatenated as numpy arrays, plus ``'frames'``.  ``prev=True``: ``call(sl, verts, before)`` with the vertices of
+        every frame's predecessor in the SEQUENCE as well (frame 0: its own); each frame's forward is computed once."""
+        e, m = self.engine, self.SMPLPY.body_model
+        T, N = self.num_frames, self.num_people
+        parts = []
+        with torch.cuda.device(self.device), torch.no_grad():
+            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
+            for f0 in range(0, len(idx), chunk):
+                sl = slice(f0, min(len(idx), f0 + chunk))
+                fr = idx[sl]
+                need = np.unique(np.concatenate([fr, fr[fr > 0] - 1])) if prev else fr      # with predecessors: each once
+                sel = torch.as_tensor(need, device=self.device)
+                nb = len(need) * N
+                verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[sel].reshape(nb, 72), e.leaf('xscale').view(N),
+                                               pT_all[sel].reshape(nb, 3), want_vposed=False)
+                verts = verts.view(len(need), N, -1, 3)
+                if prev:
+                    at = torch.as_tensor(np.searchsorted(need, fr), device=self.device)
+                    before = torch.as_tensor(np.searchsorted(need, np.maximum(fr - 1, 0)), device=self.device)
+                    got = call(sl, verts[at].contiguous(), verts[before].contiguous())
+                else:
+                    got = call(sl, verts)
+                parts.append({k: v.cpu().numpy() for k, v in got.items()})
+                del verts, got
+        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+        out['frames'] = idx
+        return out
+
     # -- the fit as images (the reference looks at it with scatter plots of projected vertices, predict.py:195-243) ------
     def render_scene(self, frames=None, images=True, **kw):
         """Render the current leaves at ``frames`` (default: all): the vertices of ``predict`` (LBS, scale, translation)
@@ -686,40 +740,17 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         ``mhhip.raster.render_scene`` (palette, light, ambient, alpha, outputs, chunk).  Reads the leaves only: buffers
         and rasteriser workspace of its own, nothing of the engine's state is written."""
         from mhhip import raster
-        if self.engine is None:
-            raise RuntimeError('render_scene: nothing to render before init_optimized_variables()')
-        if self._world()[0] > 1:
-            raise RuntimeError('render_scene is not available in a frame-sharded run (world > 1): render from the gathered '
-                               'result of get_optimized_variables() in one process')
-        e = self.engine
-        T, N = self.num_frames, self.num_people
-        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
-        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
-            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
-        idx = idx.astype(np.int64)
+        idx, chunk = self._diag_frames('render_scene', 'render from', frames, kw.pop('chunk', 32))
+        T = self.num_frames
         imgs = None
         if images and getattr(self, '_staged', False) and getattr(self, '_images', None) is not None:
             imgs = np.asarray(self._images)
             if imgs.shape != (T, self.img_h, self.img_w, 3):
                 raise ValueError('staged images are %s, not (T,H,W,3) = (%d,%d,%d,3)' % (imgs.shape, T, self.img_h, self.img_w))
             imgs = np.ascontiguousarray(imgs[idx]).astype(np.uint8)
-        chunk = max(1, int(kw.pop('chunk', 32)))
-        sel = torch.as_tensor(idx, device=self.device)
-        with torch.cuda.device(self.device), torch.no_grad():
-            pT = e.leaf('poses_T').view(T, N, 3)[sel]
-            pose = e.leaf('poses_smpl').view(T, N, 72)[sel]
-            parts = []
-            for f0 in range(0, len(idx), chunk):
-                sl = slice(f0, min(len(idx), f0 + chunk))
-                nb = (sl.stop - sl.start) * N
-                verts, _, _, _ = self.SMPLPY.body_model.lbs_forward(e.leaf('betas').view(N, 10), pose[sl].reshape(nb, 72),
-                                                                    e.leaf('xscale').view(N), pT[sl].reshape(nb, 3), want_vposed=False)
-                got = raster.render_scene(self.SMPLPY.body_model, verts.view(sl.stop - sl.start, N, -1, 3), self.cam_K,
-                                          (self.img_w, self.img_h), images=None if imgs is None else imgs[sl], chunk=chunk, **kw)
-                parts.append({k: v.cpu().numpy() for k, v in got.items()})
-        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-        out['frames'] = idx
-        return out
+        return self._diag_chunks(idx, chunk, lambda sl, verts: raster.render_scene(
+            self.SMPLPY.body_model, verts, self.cam_K, (self.img_w, self.img_h), images=None if imgs is None else imgs[sl],
+            chunk=chunk, **kw))
 
     # -- the fit from the side or from above (the reference opens an Open3D window, visualization.py) ---------------------
     def render_view(self, view, frames=None, image_size=None, K=None, scene=True, splat=1.0, **kw):
@@ -734,17 +765,7 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         then the scene) -- plus ``'frames'``.  ``kw`` goes to ``mhhip.view.render_view`` (palette, light, ambient, background,
         near, max_half, outputs, chunk).  Reads the leaves only: buffers of its own, nothing of the engine's state is written."""
         from mhhip import view as mhview
-        if self.engine is None:
-            raise RuntimeError('render_view: nothing to render before init_optimized_variables()')
-        if self._world()[0] > 1:
-            raise RuntimeError('render_view is not available in a frame-sharded run (world > 1): render from the gathered '
-                               'result of get_optimized_variables() in one process')
-        e = self.engine
-        T, N = self.num_frames, self.num_people
-        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
-        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
-            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
-        idx = idx.astype(np.int64)
+        idx, chunk = self._diag_frames('render_view', 'render from', frames, kw.pop('chunk', 32))
         size = (self.img_w, self.img_h) if image_size is None else (int(image_size[0]), int(image_size[1]))
         K = self.cam_K if K is None else K
         R, t = mhview._views(view, len(idx))
@@ -761,25 +782,11 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
                                                             np.asarray(found[1]).reshape(self.img_h, self.img_w), self.cam_K, img, splat)
             if len(cloud) == 0:
                 cloud = rgb = extent = None
-        chunk = max(1, int(kw.pop('chunk', 32)))
-        sel = torch.as_tensor(idx, device=self.device)
-        with torch.cuda.device(self.device), torch.no_grad():
-            pT = e.leaf('poses_T').view(T, N, 3)[sel]
-            pose = e.leaf('poses_smpl').view(T, N, 72)[sel]
-            if cloud is not None:
-                cloud, rgb, extent = (torch.as_tensor(a).to(self.device) for a in (cloud, rgb, extent))
-            parts = []
-            for f0 in range(0, len(idx), chunk):
-                sl = slice(f0, min(len(idx), f0 + chunk))
-                nb = (sl.stop - sl.start) * N
-                verts, _, _, _ = self.SMPLPY.body_model.lbs_forward(e.leaf('betas').view(N, 10), pose[sl].reshape(nb, 72),
-                                                                    e.leaf('xscale').view(N), pT[sl].reshape(nb, 3), want_vposed=False)
-                got = mhview.render_view(self.SMPLPY.body_model, verts.view(sl.stop - sl.start, N, -1, 3), (R[sl], t[sl]), K, size,
-                                         cloud=cloud, cloud_rgb=rgb, cloud_size_m=extent, chunk=chunk, **kw)
-                parts.append({k: v.cpu().numpy() for k, v in got.items()})
-        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-        out['frames'] = idx
-        return out
+        if cloud is not None:
+            cloud, rgb, extent = (torch.as_tensor(a).to(self.device) for a in (cloud, rgb, extent))
+        return self._diag_chunks(idx, chunk, lambda sl, verts: mhview.render_view(
+            self.SMPLPY.body_model, verts, (R[sl], t[sl]), K, size, cloud=cloud, cloud_rgb=rgb, cloud_size_m=extent,
+            chunk=chunk, **kw))
 
     # -- the fit in numbers (the reference has scatter plots to look at, predict.py:141-257) -----------------------------
     def fit_report(self, frames=None, margin=0.05, chunk=32):
@@ -795,19 +802,10 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         forward is computed when it is not among ``frames``.  At most ``chunk`` frames are on the device at a time.  Reads
         the leaves only: buffers and rasteriser workspace of its own, nothing of the engine's state is written."""
         from mhhip import report
-        if self.engine is None:
-            raise RuntimeError('fit_report: nothing to report before init_optimized_variables()')
-        if self._world()[0] > 1:
-            raise RuntimeError('fit_report is not available in a frame-sharded run (world > 1): report on the gathered '
-                               'result of get_optimized_variables() in one process')
+        idx, chunk = self._diag_frames('fit_report', 'report on', frames, chunk)
         e = self.engine
         T, N = self.num_frames, self.num_people
         H, W = self.img_h, self.img_w
-        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
-        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
-            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
-        idx = idx.astype(np.int64)
-        chunk = max(1, int(chunk))
         scene = getattr(self, '_report_scene', None)
         if scene is None and self.scene_depth is not None and getattr(self, 'scene_mask', None) is not None:
             scene = (self.scene_depth, self.scene_mask)
@@ -818,35 +816,23 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         min_z, max_z = g['min_z'].reshape(T).astype(np.float32), g['max_z'].reshape(T).astype(np.float32)
         pose2d = e.pose2d.view(T, N, 17, 3) if staged else torch.as_tensor(self._pose2d_init).to(self.device)
         m = self.SMPLPY.body_model
-        parts = []
-        with torch.cuda.device(self.device), torch.no_grad():
-            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
-            for f0 in range(0, len(idx), chunk):
-                fr = idx[f0:f0 + chunk]
-                need = np.unique(np.concatenate([fr, fr[fr > 0] - 1]))        # the frames and their predecessors, each once
-                sel = torch.as_tensor(need, device=self.device)
-                nb = len(need) * N
-                vall, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[sel].reshape(nb, 72), e.leaf('xscale').view(N),
-                                              pT_all[sel].reshape(nb, 3), want_vposed=False)
-                vall = vall.view(len(need), N, -1, 3)
-                at = torch.as_tensor(np.searchsorted(need, fr), device=self.device)
-                before = torch.as_tensor(np.searchsorted(need, np.maximum(fr - 1, 0)), device=self.device)
-                verts, prev = vall[at].contiguous(), vall[before].contiguous()
-                cur = torch.as_tensor(fr, device=self.device)
-                joints = m.joints_regress(self._joints_reg[0], verts.view(len(fr) * N, -1, 3), corr=pT_all[cur].reshape(len(fr) * N, 3),
-                                          root=self._joints_reg[1])
-                got = report.fit_report(
-                    m, verts, self.cam_K, (W, H), bits=e.bits[cur] if imgs else None, disp=e.depths[cur] if imgs else None,
-                    min_z=min_z[fr] if imgs else None, max_z=max_z[fr] if imgs else None,
-                    scene_depth=None if scene is None else np.asarray(scene[0], np.float32),
-                    scene_mask=None if scene is None else np.asarray(scene[1]) != 0, scene_points=cloud,
-                    joints=joints.view(len(fr), N, 17, 3), pose2d=pose2d[cur], cam_dist_coef=self.cam_dist_coef,
-                    joint_confidence_thr=self.joint_confidence_thr, verts_prev=prev, has_prev=fr > 0, margin=margin, chunk=chunk)
-                parts.append({k: v.cpu().numpy() for k, v in got.items()})
-                del vall, verts, prev, got
-        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
+        def report_chunk(sl, verts, prev):
+            fr = idx[sl]
+            cur = torch.as_tensor(fr, device=self.device)
+            joints = m.joints_regress(self._joints_reg[0], verts.view(len(fr) * N, -1, 3),
+                                      corr=e.leaf('poses_T').view(T, N, 3)[cur].reshape(len(fr) * N, 3), root=self._joints_reg[1])
+            return report.fit_report(
+                m, verts, self.cam_K, (W, H), bits=e.bits[cur] if imgs else None, disp=e.depths[cur] if imgs else None,
+                min_z=min_z[fr] if imgs else None, max_z=max_z[fr] if imgs else None,
+                scene_depth=None if scene is None else np.asarray(scene[0], np.float32),
+                scene_mask=None if scene is None else np.asarray(scene[1]) != 0, scene_points=cloud,
+                joints=joints.view(len(fr), N, 17, 3), pose2d=pose2d[cur], cam_dist_coef=self.cam_dist_coef,
+                joint_confidence_thr=self.joint_confidence_thr, verts_prev=prev, has_prev=fr > 0, margin=margin, chunk=chunk)
+
+        out = self._diag_chunks(idx, chunk, report_chunk, prev=True)
         out['valid'] = self._valid.reshape(T, N)[idx].copy()
-        out['frames'] = idx
+        out['frames'] = out.pop('frames')          # stays the last key
         return out
 
     # -- who stands in front of whom, against the instance masks ----------------------------------------------------------
@@ -858,40 +844,23 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         and the gate are the staged ones (a fit, or ``_stage_from_dataloader``, must have run); ``margin`` / ``delta`` default
         to the optimiser's ``order_margin`` / ``order_delta``.  Reads the leaves only, on a rasteriser workspace of its own."""
         from mhhip import order
-        if self.engine is None:
-            raise RuntimeError('order_report: nothing to report before init_optimized_variables()')
-        if self._world()[0] > 1:
-            raise RuntimeError('order_report is not available in a frame-sharded run (world > 1): report on the gathered '
-                               'result of get_optimized_variables() in one process')
+
+        def staged_masks():
+            if not (bool(getattr(self, '_staged', False)) and self.engine.has_images):
+                raise RuntimeError('order_report needs the staged instance masks: run fit() (or stage a dataloader with masks) first')
+
+        idx, chunk = self._diag_frames('order_report', 'report on', frames, chunk, need=staged_masks)
         e = self.engine
-        if not (bool(getattr(self, '_staged', False)) and e.has_images):
-            raise RuntimeError('order_report needs the staged instance masks: run fit() (or stage a dataloader with masks) first')
-        T, N = self.num_frames, self.num_people
-        H, W = self.img_h, self.img_w
-        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
-        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
-            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
-        idx = idx.astype(np.int64)
-        chunk = max(1, int(chunk))
         margin = self.order_margin if margin is None else float(margin)
         delta = self.order_delta if delta is None else float(delta)
-        m = self.SMPLPY.body_model
-        parts = []
-        with torch.cuda.device(self.device), torch.no_grad():
-            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
-            gate = (e.p2d_valid * e.mask_valid).view(T, N)
-            for f0 in range(0, len(idx), chunk):
-                cur = torch.as_tensor(idx[f0:f0 + chunk], device=self.device)
-                nb = len(cur) * N
-                verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[cur].reshape(nb, 72), e.leaf('xscale').view(N),
-                                               pT_all[cur].reshape(nb, 3), want_vposed=False)
-                got = order.order_terms(m, verts.view(len(cur), N, -1, 3), self.cam_K, (W, H), e.bits[cur], e.ebits[cur],
-                                        gate=gate[cur], margin=margin, delta=delta, chunk=chunk)
-                parts.append({k: v.cpu().numpy() for k, v in got.items()})
-                del verts, got
-        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-        out['frames'] = idx
-        return out
+        gate = (e.p2d_valid * e.mask_valid).view(self.num_frames, self.num_people)
+
+        def order_chunk(sl, verts):
+            cur = torch.as_tensor(idx[sl], device=self.device)
+            return order.order_terms(self.SMPLPY.body_model, verts, self.cam_K, (self.img_w, self.img_h), e.bits[cur], e.ebits[cur],
+                                     gate=gate[cur], margin=margin, delta=delta, chunk=chunk)
+
+        return self._diag_chunks(idx, chunk, order_chunk)
 
     # -- which part of a body touches the scene (the reference has its interactive viewer to look at) ----------------------
     def contact_map(self, frames=None, radius=0.1, contact=0.03, nearest=False, chunk=32):
@@ -904,38 +873,16 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         most ``chunk`` frames are on the device at a time.  Reads the leaves only: a grid and buffers of its own, nothing of
         the engine's state is written."""
         from mhhip import contact as mhcontact
-        if self.engine is None:
-            raise RuntimeError('contact_map: nothing to measure before init_optimized_variables()')
-        if self._world()[0] > 1:
-            raise RuntimeError('contact_map is not available in a frame-sharded run (world > 1): measure on the gathered '
-                               'result of get_optimized_variables() in one process')
-        if self.scene_pcd is None or int(self.scene_pcd.numel()) == 0:
-            raise RuntimeError('contact_map needs a scene: hand one in with update_scene_pointcloud(scene_depth, scene_mask), or '
-                               "run fit() with scene_update='device' for more than 30 cycles")
-        e = self.engine
-        T, N = self.num_frames, self.num_people
-        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
-        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
-            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
-        idx = idx.astype(np.int64)
-        chunk = max(1, int(chunk))
-        m = self.SMPLPY.body_model
+
+        def a_scene():
+            if self.scene_pcd is None or int(self.scene_pcd.numel()) == 0:
+                raise RuntimeError('contact_map needs a scene: hand one in with update_scene_pointcloud(scene_depth, scene_mask), or '
+                                   "run fit() with scene_update='device' for more than 30 cycles")
+
+        idx, chunk = self._diag_frames('contact_map', 'measure on', frames, chunk, need=a_scene)
         cloud = self.scene_pcd.view(-1, 3)
-        parts = []
-        with torch.cuda.device(self.device), torch.no_grad():
-            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
-            for f0 in range(0, len(idx), chunk):
-                cur = torch.as_tensor(idx[f0:f0 + chunk], device=self.device)
-                nb = len(cur) * N
-                verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[cur].reshape(nb, 72), e.leaf('xscale').view(N),
-                                               pT_all[cur].reshape(nb, 3), want_vposed=False)
-                got = mhcontact.contact_map(m, verts.view(len(cur), N, -1, 3), cloud, radius=radius, contact=contact, nearest=nearest,
-                                            chunk=chunk)
-                parts.append({k: v.cpu().numpy() for k, v in got.items()})
-                del verts, got
-        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-        out['frames'] = idx
-        return out
+        return self._diag_chunks(idx, chunk, lambda sl, verts: mhcontact.contact_map(
+            self.SMPLPY.body_model, verts, cloud, radius=radius, contact=contact, nearest=nearest, chunk=chunk))
 
     # -- which people touch, where and with which parts (again the reference has its viewer only) --------------------------
     def proximity_map(self, frames=None, radius=0.1, contact=0.02, nearest=False, chunk=8):
@@ -950,35 +897,10 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         frames are on the device at a time.  Needs no scene and no staged images.  Reads the leaves only: a workspace and
         buffers of its own, nothing of the engine's state is written."""
         from mhhip import proximity as mhprox
-        if self.engine is None:
-            raise RuntimeError('proximity_map: nothing to measure before init_optimized_variables()')
-        if self._world()[0] > 1:
-            raise RuntimeError('proximity_map is not available in a frame-sharded run (world > 1): measure on the gathered '
-                               'result of get_optimized_variables() in one process')
-        e = self.engine
-        T, N = self.num_frames, self.num_people
-        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
-        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
-            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
-        idx = idx.astype(np.int64)
-        chunk = max(1, int(chunk))
-        m = self.SMPLPY.body_model
-        live = self._valid.reshape(T, N) > 0
-        parts = []
-        with torch.cuda.device(self.device), torch.no_grad():
-            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
-            for f0 in range(0, len(idx), chunk):
-                cur = torch.as_tensor(idx[f0:f0 + chunk], device=self.device)
-                nb = len(cur) * N
-                verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[cur].reshape(nb, 72), e.leaf('xscale').view(N),
-                                               pT_all[cur].reshape(nb, 3), want_vposed=False)
-                got = mhprox.proximity_map(m, verts.view(len(cur), N, -1, 3), live=live[idx[f0:f0 + chunk]], radius=radius,
-                                           contact=contact, nearest=nearest, chunk=chunk)
-                parts.append({k: v.cpu().numpy() for k, v in got.items()})
-                del verts, got
-        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-        out['frames'] = idx
-        return out
+        idx, chunk = self._diag_frames('proximity_map', 'measure on', frames, chunk)
+        live = self._valid.reshape(self.num_frames, self.num_people) > 0
+        return self._diag_chunks(idx, chunk, lambda sl, verts: mhprox.proximity_map(
+            self.SMPLPY.body_model, verts, live=live[idx[sl]], radius=radius, contact=contact, nearest=nearest, chunk=chunk))
 
     # -- is one body inside another (the reference has a nearest-face-normal heuristic, unused) -------------------------------
     def penetration_map(self, frames=None, chunk=8):
@@ -992,34 +914,10 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         Needs no scene and no staged images.  Reads the leaves only: a workspace and buffers of its own, nothing of the
         engine's state is written."""
         from mhhip import inside as mhinside
-        if self.engine is None:
-            raise RuntimeError('penetration_map: nothing to measure before init_optimized_variables()')
-        if self._world()[0] > 1:
-            raise RuntimeError('penetration_map is not available in a frame-sharded run (world > 1): measure on the gathered '
-                               'result of get_optimized_variables() in one process')
-        e = self.engine
-        T, N = self.num_frames, self.num_people
-        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
-        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
-            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
-        idx = idx.astype(np.int64)
-        chunk = max(1, int(chunk))
-        m = self.SMPLPY.body_model
-        live = self._valid.reshape(T, N) > 0
-        parts = []
-        with torch.cuda.device(self.device), torch.no_grad():
-            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
-            for f0 in range(0, len(idx), chunk):
-                cur = torch.as_tensor(idx[f0:f0 + chunk], device=self.device)
-                nb = len(cur) * N
-                verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[cur].reshape(nb, 72), e.leaf('xscale').view(N),
-                                               pT_all[cur].reshape(nb, 3), want_vposed=False)
-                got = mhinside.penetration_map(m, verts.view(len(cur), N, -1, 3), live=live[idx[f0:f0 + chunk]], chunk=chunk)
-                parts.append({k: v.cpu().numpy() for k, v in got.items()})
-                del verts, got
-        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-        out['frames'] = idx
-        return out
+        idx, chunk = self._diag_frames('penetration_map', 'measure on', frames, chunk)
+        live = self._valid.reshape(self.num_frames, self.num_people) > 0
+        return self._diag_chunks(idx, chunk, lambda sl, verts: mhinside.penetration_map(
+            self.SMPLPY.body_model, verts, live=live[idx[sl]], chunk=chunk))
 
     # -- how deep along the shortest way out, and how much room between bodies that do not overlap -------------------------------
     def clearance_map(self, frames=None, radius=0.1, contact=0.02, nearest=False, chunk=8):
@@ -1036,35 +934,10 @@ class SMPLDepthSequenceOptimizer(SMPLOptimizerBase):
         no staged images.  Reads the leaves only: workspaces and buffers of its own, nothing of the engine's state is
         written."""
         from mhhip import surface as mhsurface
-        if self.engine is None:
-            raise RuntimeError('clearance_map: nothing to measure before init_optimized_variables()')
-        if self._world()[0] > 1:
-            raise RuntimeError('clearance_map is not available in a frame-sharded run (world > 1): measure on the gathered '
-                               'result of get_optimized_variables() in one process')
-        e = self.engine
-        T, N = self.num_frames, self.num_people
-        idx = np.arange(T) if frames is None else np.asarray(frames).reshape(-1)
-        if idx.size == 0 or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= T:
-            raise ValueError('frames must be indices in [0, %d), got %r' % (T, frames))
-        idx = idx.astype(np.int64)
-        chunk = max(1, int(chunk))
-        m = self.SMPLPY.body_model
-        live = self._valid.reshape(T, N) > 0
-        parts = []
-        with torch.cuda.device(self.device), torch.no_grad():
-            pT_all, pose_all = e.leaf('poses_T').view(T, N, 3), e.leaf('poses_smpl').view(T, N, 72)
-            for f0 in range(0, len(idx), chunk):
-                cur = torch.as_tensor(idx[f0:f0 + chunk], device=self.device)
-                nb = len(cur) * N
-                verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), pose_all[cur].reshape(nb, 72), e.leaf('xscale').view(N),
-                                               pT_all[cur].reshape(nb, 3), want_vposed=False)
-                got = mhsurface.clearance_map(m, verts.view(len(cur), N, -1, 3), live=live[idx[f0:f0 + chunk]], radius=radius,
-                                              contact=contact, nearest=nearest, chunk=chunk)
-                parts.append({k: v.cpu().numpy() for k, v in got.items()})
-                del verts, got
-        out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-        out['frames'] = idx
-        return out
+        idx, chunk = self._diag_frames('clearance_map', 'measure on', frames, chunk)
+        live = self._valid.reshape(self.num_frames, self.num_people) > 0
+        return self._diag_chunks(idx, chunk, lambda sl, verts: mhsurface.clearance_map(
+            self.SMPLPY.body_model, verts, live=live[idx[sl]], radius=radius, contact=contact, nearest=nearest, chunk=chunk))
 
     # -- reference optimizer.py:664-675 ---------------------------------------------------------------
     def one_euro_filter(self, x, min_cutoff=0.1, beta=0.02, frame_rate=25):

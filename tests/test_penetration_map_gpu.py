@@ -53,8 +53,8 @@ class _Copy:
 
 
 def _faces(opt):
-    from mhhip import inside
-    return inside._faces_of(opt.SMPLPY.body_model).astype(np.int64)
+    from mhhip import bodies
+    return bodies.faces_of(opt.SMPLPY.body_model).astype(np.int64)
 
 
 def _metres(lat):

@@ -14,16 +14,10 @@ import argparse
 import csv
 import json
 import os
-import sys
-import tempfile
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, 'scene-aware-3d-multi-human_amd')):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import map_common as mc                                    # (puts the packages on sys.path)
 
 
 def colours(dist, contact, radius):
@@ -50,50 +44,20 @@ def write_ply(path, verts, faces, rgb):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--people', type=int, default=2)
-    ap.add_argument('--frames', type=int, default=8)
-    ap.add_argument('--size', type=int, nargs=2, default=(240, 135), metavar=('W', 'H'))
-    ap.add_argument('--cycles', type=int, default=40, help='fit cycles before the map (0: the initial variables)')
-    ap.add_argument('--init-iter', type=int, default=30)
+    mc.add_arguments(ap, chunk=32, together=False)
     ap.add_argument('--floor', type=float, default=1.15, help='height of the injected floor below the camera axis in metres')
     ap.add_argument('--radius', type=float, default=0.1)
     ap.add_argument('--contact', type=float, default=0.03)
-    ap.add_argument('--chunk', type=int, default=32)
-    ap.add_argument('--repeat', type=int, default=1, help='calls (the last one is written, all are timed)')
-    ap.add_argument('--ply', action='store_true', help='one coloured mesh per frame')
     ap.add_argument('--out', default='contact_out')
-    ap.add_argument('--seed', type=int, default=5)
     a = ap.parse_args()
-    import torch
-    from mhhip import build, contact, synthetic, synthetic_seq
-    from mhmocap.optimizer import SMPLDepthSequenceOptimizer
-    build.build()
-    struct = synthetic.make_smpl_struct(1)
-    regs = synthetic.make_extra_regressors(1, struct)
-    tmp = tempfile.mkdtemp()
-    for k, fn in [('extra9', 'J_regressor_extra.npy'), ('h36m', 'J_regressor_h36m.npy'),
-                  ('alphapose', 'SMPL_AlphaPose_Regressor_RMSprop_6.npy')]:
-        np.save(os.path.join(tmp, fn), regs[k])
+    from mhhip import contact
+    opt, seq, K = mc.setup(a)
     (W, H), T, N = a.size, a.frames, a.people
-    K = synthetic.default_cam_K((W, H), 60.0)
-    opt = SMPLDepthSequenceOptimizer(
-        image_size=(W, H), num_frames=T, cam_K=K, device='cuda:0', smpl_model_parameters_path=tmp, smpl_data_struct=struct,
-        scene_update='none', proj2d_loss_coef=1.0, depth_loss_coef=0.05, silhouette_loss_coef=0.1, reg_velocity_coef=0.05,
-        reg_verts_filter_coef=0.002, reg_poses_coef=0.002, reg_scales_coef=1e-4, reg_contact_coef=0.001, reg_foot_sliding_coef=0.01)
-    seq = synthetic_seq.make_sequence(opt.SMPLPY.body_model, N, T, (W, H), a.seed, cam_K=K)
     ys = (np.arange(H, dtype=np.float32) + 0.5 - K[1, 2]) / K[1, 1]
     depth = np.minimum(np.where(ys[:, None] > 1e-3, a.floor / np.maximum(ys[:, None], 1e-3), 10.0), 10.0)
-    opt.init_optimized_variables(seq['pose2d'], seq['poses_smpl'], seq['betas_smpl'], seq['valid_smpl'], num_iter=a.init_iter)
     opt.update_scene_pointcloud(np.tile(depth, (1, W)).astype(np.float32), np.tile(ys[:, None] > 1e-3, (1, W)))
-    dl = torch.utils.data.DataLoader(synthetic_seq.SequenceDataset(seq), batch_size=min(10, T), shuffle=False)
-    if a.cycles > 0:
-        opt.fit(dl, num_iter=a.cycles)
-    wall = []
-    for _ in range(max(1, a.repeat)):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        got = opt.contact_map(radius=a.radius, contact=a.contact, chunk=a.chunk)
-        wall.append(time.perf_counter() - t0)
+    mc.fit(opt, seq, a)
+    got, wall = mc.wall_times(lambda: opt.contact_map(radius=a.radius, contact=a.contact, chunk=a.chunk), a.repeat)
     os.makedirs(a.out, exist_ok=True)
     with open(os.path.join(a.out, 'contact_map.csv'), 'w', newline='') as f:
         w = csv.writer(f)
@@ -105,11 +69,8 @@ def main():
     if a.ply:
         faces = np.asarray(opt.SMPLPY.body_model.faces).astype(np.int64)
         rgb = colours(got['dist_m'], a.contact, a.radius)
-        e, m = opt.engine, opt.SMPLPY.body_model
         for i, fr in enumerate(got['frames']):                  # the vertices the map was computed on, a frame at a time
-            verts, _, _, _ = m.lbs_forward(e.leaf('betas').view(N, 10), e.leaf('poses_smpl').view(T, N, 72)[fr], e.leaf('xscale').view(N),
-                                           e.leaf('poses_T').view(T, N, 3)[fr], want_vposed=False)
-            write_ply(os.path.join(a.out, 'contact_%04d.ply' % fr), verts.view(N, -1, 3).cpu().numpy(), faces, rgb[i])
+            write_ply(os.path.join(a.out, 'contact_%04d.ply' % fr), mc.forward(opt, [int(fr)])[0].cpu().numpy(), faces, rgb[i])
     print(json.dumps(dict(frames=T, people=N, image=[W, H], cloud_points=int(opt.scene_pcd.numel() // 3), radius=a.radius,
                           contact=a.contact, contact_verts=int(got['contact_verts'].sum()),
                           contact_map_wall_s=[round(x, 4) for x in wall])))
