@@ -344,9 +344,34 @@ extern "C" int mh_adam_step(float* params, const float* grads, float* exp_avg, f
 // =============================================================================================
 // a19: one-euro filter, sequential in t, parallel over channels
 // =============================================================================================
+// One frame of one channel.  numpy evaluates every product and sum separately in float32, so nothing here may be contracted into
+// an FMA.  The pragma governs the operators written in ITS block only: __fmul_rn / __fadd_rn are inline functions of the HIP
+// headers (plain operators there, compiled under the default -ffp-contract=fast), and a loop spelled with them comes out fused
+// (v_fma_f32 / v_fmac_f32 for r + 1, the two blends and the cutoff).  So: plain operators under the pragma, and ONE body for
+// the prefetch block and the tail loop -- a frame's bits must not depend on the loop it goes through, or a shard, which starts
+// at local frame 0, differs from the whole scan (tests/test_cycle_kernels_gpu.py holds both to the same bits).
+__device__ __forceinline__ float one_euro_step(float xi, int i, float frame_rate, float min_cutoff, float beta, float& ti,
+                                               float& tp, float& xp, float& dxp) {
+#pragma clang fp contract(off)
+  const float two_pi = 6.283185307179586f;
+  ti = ti + (float)((double)i / (double)frame_rate);        // optimizer.py:671 (float32 running sum); i: global frame index
+  const float te = ti - tp;
+  float r = two_pi * te;                                    // d_cutoff = 1
+  const float ad = r / (r + 1.f);
+  const float dx = (xi - xp) / te;
+  const float dxh = ad * dx + (1.f - ad) * dxp;
+  const float cutoff = min_cutoff + beta * fabsf(dxh);
+  r = (two_pi * cutoff) * te;
+  const float a = r / (r + 1.f);
+  const float xh = a * xi + (1.f - a) * xp;
+  xp = xh;
+  dxp = dxh;
+  tp = ti;
+  return xh;
+}
+
 __global__ void k_one_euro(const float* x, float* y, int T, size_t E, float min_cutoff, float beta, float frame_rate,
                            int i0, float t0, const float* xprev_in, const float* dxprev_in, float* dxprev_out) {
-  const float two_pi = 6.283185307179586f;
   for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < E; e += (size_t)gridDim.x * blockDim.x) {
     float xp, dxp, tp, ti;
     int first;
@@ -370,47 +395,11 @@ __global__ void k_one_euro(const float* x, float* y, int T, size_t E, float min_
 #pragma unroll
       for (int u = 0; u < 8; ++u) xv[u] = x[(size_t)(k + u) * E + e];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-#pragma clang fp contract(off)
-        const int i = i0 + k + u;
-        ti = ti + (float)((double)i / (double)frame_rate);
-        const float xi = xv[u];
-        const float te = ti - tp;
-        float r = two_pi * te;
-        const float ad = r / (r + 1.f);
-        const float dx = (xi - xp) / te;
-        const float dxh = ad * dx + (1.f - ad) * dxp;
-        const float cutoff = min_cutoff + beta * fabsf(dxh);
-        r = (two_pi * cutoff) * te;
-        const float a = r / (r + 1.f);
-        const float xh = a * xi + (1.f - a) * xp;
-        y[(size_t)(k + u) * E + e] = xh;
-        xp = xh;
-        dxp = dxh;
-        tp = ti;
-      }
+      for (int u = 0; u < 8; ++u)
+        y[(size_t)(k + u) * E + e] = one_euro_step(xv[u], i0 + k + u, frame_rate, min_cutoff, beta, ti, tp, xp, dxp);
     }
-    for (; k < T; ++k) {
-#pragma clang fp contract(off)
-      const int i = i0 + k;                                   // global frame index
-      ti = __fadd_rn(ti, (float)((double)i / (double)frame_rate));     // optimizer.py:671 (float32 running sum)
-      const float xi = x[(size_t)k * E + e];
-      // numpy evaluates every product/sum separately in float32: no FMA contraction (hip's __fmul_rn / __fadd_rn are plain
-      // operators and do not prevent it -- the pragma does)
-      const float te = __fsub_rn(ti, tp);
-      float r = __fmul_rn(two_pi, te);                        // d_cutoff = 1
-      const float ad = __fdiv_rn(r, __fadd_rn(r, 1.f));
-      const float dx = __fdiv_rn(__fsub_rn(xi, xp), te);
-      const float dxh = __fadd_rn(__fmul_rn(ad, dx), __fmul_rn(__fsub_rn(1.f, ad), dxp));
-      const float cutoff = __fadd_rn(min_cutoff, __fmul_rn(beta, fabsf(dxh)));
-      r = __fmul_rn(__fmul_rn(two_pi, cutoff), te);
-      const float a = __fdiv_rn(r, __fadd_rn(r, 1.f));
-      const float xh = __fadd_rn(__fmul_rn(a, xi), __fmul_rn(__fsub_rn(1.f, a), xp));
-      y[(size_t)k * E + e] = xh;
-      xp = xh;
-      dxp = dxh;
-      tp = ti;
-    }
+    for (; k < T; ++k)
+      y[(size_t)k * E + e] = one_euro_step(x[(size_t)k * E + e], i0 + k, frame_rate, min_cutoff, beta, ti, tp, xp, dxp);
     if (dxprev_out) dxprev_out[e] = dxp;
   }
 }
