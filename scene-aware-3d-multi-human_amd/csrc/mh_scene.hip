@@ -43,6 +43,7 @@ __global__ __launch_bounds__(256) void k_lowest_vertex(const float* verts, int V
         best = sy[w];
         bi = si[w];
       }
+    if (bi == 0x7fffffff) bi = 0;                    // nothing compares (NaN or -inf everywhere): any vertex, as mh_lowest_from_key
     low_idx[b] = bi;
     low_xyz[(size_t)b * 3] = vb[(size_t)bi * 3];
     low_xyz[(size_t)b * 3 + 1] = vb[(size_t)bi * 3 + 1];

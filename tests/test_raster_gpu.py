@@ -2,58 +2,40 @@
 against the oracle (oracle/raster_oracle.py selection + torch autograd): per-body loss values,
 dL/dverts, dL/dzmin_lin, dL/dzmax_lin.  The oracle itself is pinned analytically
 (tests/test_raster_oracle.py); PyTorch3D is unavailable, so this term is "parity unpinned"
-with respect to the reference."""
+with respect to the reference.
+
+The inputs are drawn by tests/raster_cases.py (no GPU).  N = 9, 17 and 32 people per frame -- the term indexes 32-bit words per
+pixel with the person index, bit 31 is the sign bit of the int32 tensors that hold them -- stand where raster_cases.rows_layout
+puts them; tests/test_raster_cases.py asserts from the oracle alone what such a frame has to contain.  Measured on the MI355X at
+N = 9 / 17 / 32 (printed with pytest -s; the gates are _check's): depth 5.7e-7 / 2.1e-7 / 6.7e-7 and silhouette 1.5e-5 / 1.5e-5 /
+1.2e-5 of the largest value, 2 / 0 / 0 entries of dL/dverts off by more than 2e-3 of the largest, per-body sums 9.3e-4 / 1.5e-4 /
+8.5e-5 of the largest column sum."""
 import numpy as np
 import pytest
 import torch
 
 from mhhip import synthetic
 from oracle import fit_oracle as fo
-from oracle import lbs_oracle as lo
 from oracle import raster_oracle as ro
+
+import raster_cases as rc
+from raster_cases import _scene  # noqa: F401  (the scene of every case here; with a layout: people where the layout puts them)
 
 pytestmark = pytest.mark.gpu
 
 
-def _scene(T, N, W, H, seed, zlo, zhi):
-    rng = np.random.RandomState(seed)
-    sp = synthetic.make_sequence_params(N, T, seed)
-    pT = sp['trans_gt'].copy()
-    pT[..., 2] = rng.uniform(zlo, zhi, (T, N))
-    pT[..., 0] = rng.uniform(-0.25, 0.25, (T, N)) * pT[..., 2]
-    pT[..., 1] = rng.uniform(-0.05, 0.1, (T, N))
-    return sp, pT.astype(np.float32), rng
-
-
-def _run_case(smpl_struct, smpl_regs, T, N, W, H, seed, zlo=3.0, zhi=6.0, fov=60.0, hip_selection=False, oracle_dtype=torch.float32, coefs=None):
+def _run_case(smpl_struct, smpl_regs, T, N, W, H, seed, zlo=3.0, zhi=6.0, fov=60.0, hip_selection=False, oracle_dtype=torch.float32, coefs=None,
+              layout=None):
     from mhhip import engine
     from mhhip.sequence import SequenceEngine
     from mhhip.raster import RasterTerms
-    K = synthetic.default_cam_K((W, H), fov)
-    sp, pT, rng = _scene(T, N, W, H, seed, zlo, zhi)
+    inp = rc.inputs(smpl_struct, smpl_regs, T, N, W, H, seed, zlo, zhi, fov, layout)     # _scene, the masks, the depth maps
+    K, sp, pT, faces, betas, zmin, zmax = (inp[k] for k in ('K', 'sp', 'pT', 'faces', 'betas', 'zmin', 'zmax'))
+    seg, depths, pose2d = inp['seg'], inp['depths'], inp['pose2d']
     model = engine.BodyModel(smpl_struct, smpl_regs)
-    omodel = lo.BodyModel(smpl_struct, smpl_regs)
-    faces = np.asarray(smpl_struct.f).astype(np.int64)
-    betas = sp['betas_gt']
     coefs = dict(coefs or dict(depth=0.05, silhouette=0.1))
     e = SequenceEngine(model, (W, H), T, N, K, None, coefs, batch_size=2)
-    zmin = rng.uniform(0.5, 1.5, T).astype(np.float32)
-    zmax = rng.uniform(4.0, 9.0, T).astype(np.float32)
-    e.set_leaves(pT, sp['poses_gt'], betas, zmin, zmax, rng.normal(0, 0.5, N).astype(np.float32))
-    # masks: silhouette of a slightly different pose, so that alpha - seg is non-trivial
-    with torch.no_grad():
-        be = torch.tensor(betas)[None].expand(T, N, 10).reshape(-1, 10)
-        out = lo.smpl_forward(omodel, be, torch.tensor(sp['poses_init']).view(-1, 72))
-        s = torch.pow(torch.tensor(1.1), e.leaf('xscale').cpu())[None, :, None, None]
-        v0 = s * out['verts'].view(T, N, -1, 3) + torch.tensor(pT).view(T, N, 1, 3) + torch.tensor([0.03, -0.02, 0.0])
-        _, a0 = ro.render(v0.view(T * N, -1, 3), faces, K, (W, H))
-    seg = (a0.view(T, N, H, W) > 0.5).float().numpy()
-    seg[0, 0] = 0                                                  # an empty mask
-    depths = rng.uniform(0, 1, (T, H, W)).astype(np.float32)
-    pose2d = np.zeros((T, N, 17, 3), np.float32)
-    pose2d[..., 2] = 0.9
-    if T > 1:
-        pose2d[1, N - 1, :, 2] = 0.1                               # a body without a valid 2D pose
+    e.set_leaves(pT, sp['poses_gt'], betas, zmin, zmax, inp['xscale'])
     e.stage(pose2d, sp['poses_init'], sp['valid'], betas, seg, depths)
     e.forward()
     L = __import__('mhhip._lib', fromlist=['lib']).lib()
@@ -108,7 +90,8 @@ def _run_case(smpl_struct, smpl_regs, T, N, W, H, seed, zlo=3.0, zhi=6.0, fov=60
                 want_depth=depth_tn.detach().numpy(), sil=e.sil_body.cpu().numpy().reshape(T, N), want_sil=want_sil,
                 gzmin=e.leaf('zmin_lin', e.grads).cpu().numpy(), gzmax=e.leaf('zmax_lin', e.grads).cpu().numpy(),
                 want_gzmin=tzmin.grad.numpy(), want_gzmax=tzmax.grad.numpy(), log=log.cpu().numpy(),
-                zbuf=zbuf.detach().numpy(), sel=sel, faces=faces, K=K, verts=e.verts.cpu().numpy(), shape=(T, N, H, W))
+                zbuf=zbuf.detach().numpy(), alpha=alpha.detach().numpy(), seg=seg, pT=pT, pose2d=pose2d, sel=sel, faces=faces, K=K,
+                verts=e.verts.cpu().numpy(), shape=(T, N, H, W))
 
 
 def _hip_selection(sel, B, H, W):
@@ -345,3 +328,41 @@ def test_face_straddling_the_camera_plane_is_skipped_whole():
     ndc = ro.to_ndc(verts.cpu(), K, (W, H)).numpy().astype(np.float32)
     f8, _ = ro.select_faces(ndc, faces.astype(np.int64), H, W, 1e-4, 8)
     assert (f8[0] == -1).all() and ((f8[1, ..., 0] >= 0) == (zbuf[1] > 0)).mean() > 0.995
+
+
+# ---- 9, 17 and 32 people per frame --------------------------------------------------------------------------------------
+# mh_raster_terms indexes 32-bit words per pixel with the person index ((ebits >> n) & 1, (bits >> n) & 1, bits & front[b]).
+# raster_cases.rows_layout BUILDS the frame -- staggered rows on a stand, every person at a depth of its own, person N - 1
+# nearest -- since 32 people placed the way _scene draws them leave most of them without an uncovered mask pixel.
+def _crowd(smpl_struct, smpl_regs, name):
+    r = _run_case(smpl_struct, smpl_regs, **rc.CROWDS[name])
+    # what the case has to contain, on the oracle's side: its render of the engine's vertices, the masks, the translations
+    print(name, rc.crowd_conditions(r['seg'], r['pT'], r['pose2d'], r['zbuf'], r['alpha']))
+    T, N, H, W = r['shape']
+    rel = lambda g, w: float(np.abs(g - w).max() / np.abs(w).max())
+    scale = np.abs(r['want_gv']).max()
+    print('%s measured (the gates are _check\'s): depth %.1e, silhouette %.1e, gzmin %.1e, gzmax %.1e of the largest entry; dL/dverts: '
+          '%d entries off by more than 2e-3 of the largest (6 allowed), largest %.1e, per-body sums %.1e of the largest column sum (5e-3)'
+          % (name, rel(r['depth'], r['want_depth']), rel(r['sil'], r['want_sil']), rel(r['gzmin'], r['want_gzmin']),
+             rel(r['gzmax'], r['want_gzmax']), int((np.abs(r['gv'] - r['want_gv']) > 2e-3 * scale).sum()), rel(r['gv'], r['want_gv']),
+             np.abs(r['gv'].sum(axis=1) - r['want_gv'].sum(axis=1)).max() / np.abs(r['want_gv']).sum(axis=1).max()))
+    assert (r['want_sil'][:, N - 1] > 0).all() and (r['want_depth'] > 0).sum() >= 3 * T * N // 4
+    if N == 32:                                                    # bit 31: the sign bit of the int32 tensors that hold the words
+        e = r['e']
+        assert int((e.bits.view(torch.int32) < 0).sum()) >= 20 and int((e.ebits.view(torch.int32) < 0).sum()) > 0
+        assert int((e.front.view(torch.int32) < 0).sum()) == T * (N - 1)
+    return r
+
+
+@pytest.mark.parametrize('name', ['n9', 'n17', 'n32'])
+def test_raster_terms_crowd(smpl_struct, smpl_regs, name):
+    _check(_crowd(smpl_struct, smpl_regs, name))
+
+
+def test_raster_terms_crowd_of_32_deterministic_scatter(smpl_struct, smpl_regs):
+    from mhhip.raster import set_deterministic
+    old = set_deterministic(True)
+    try:
+        _check(_crowd(smpl_struct, smpl_regs, 'n32'))
+    finally:
+        set_deterministic(old)
